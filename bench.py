@@ -12,6 +12,9 @@ forward (networks.VNet, batch-statistics BN) + softmax/Sorensen-Dice + backward 
 replayed hipGraph of the whole step (2 eager steps + 1 capture happen before the W warm-up steps; VNET_STEP_GRAPH=0
 gives the kernel-by-kernel eager enqueue).  Rank 0 prints ONE JSON line.
 
+A plain run measures the headline only: set-up, warm-up, the K timed steps, `--dump-outputs DIR` if given, the JSON line.
+Everything below runs only with `--full` (its `--no-*` switches then drop single legs):
+
 `roofline`: HIP events around every launch of the dominant kernel family -- decoder level 1 / conv_1, the 5x5x5
 convolution with 16 output channels at 128^3: forward (32->16), backward-data (16->32) and filter gradient, 268.4 GF
 algorithmic each.  Events cannot be timed inside a replayed hipGraph on this runtime (profiles/probes/graph_event_probe.py),
@@ -43,6 +46,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: roofline, sustained, hbm_kernels, c5_bf16, the other fp32 mode, "
+                         "c2_64cube_b2, cpu_baseline (off: the headline step alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed as DIR/<name>.npy (loss, seeded samples of the "
+                         "parameters and their gradients)")
     ap.add_argument("--patch", type=int, default=128)
     ap.add_argument("--batch", type=int, default=1, help="patches per GPU per step (weak scaling)")
     ap.add_argument("--channels", type=int, default=1)
@@ -316,8 +325,31 @@ def family_tags(P, B, bf16, x3=False):
     return {"%s k5 s1 %d^3x%d 32->16" % (c, P, B), "%s k5 s1 %d^3x%d 16->32" % (c, P, B), "%s k5 s1 %d^3x%d 32->16" % (w, P, B)}
 
 
-def measure(args, patch, batch, channels, classes, compute, rank, local, world):
-    """Build the model, run prepare + warm-up + the timed K steps + the roofline replays.  Returns the result dict."""
+DUMP_SAMPLE = 1 << 22      # parameters / gradients written per array: 16 MB each in float32
+
+
+def dump_outputs(path, m, loss):
+    """What train_step leaves a caller after the last timed step: its loss and the flat parameter and gradient vectors (43.9M floats
+    each at the default network, so a fixed sample of DUMP_SAMPLE positions drawn from seed 0, in ascending order)."""
+    import numpy as np
+    import torch
+    flat = m.flat
+    n = flat.numel
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(idx).to(flat.data.device)
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1), "params": flat.data, "grads": flat.grad}
+    for name, t in arrays.items():
+        if name != "loss" and idx is not None:
+            t = t[idx]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
+def measure(args, patch, batch, channels, classes, compute, rank, local, world, dump=None):
+    """Build the model, run prepare + warm-up + the timed K steps (+ with --full the roofline and sustained replays).  dump: directory
+    for dump_outputs() after the timed steps.  Returns the result dict."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -354,14 +386,15 @@ def measure(args, patch, batch, channels, classes, compute, rank, local, world):
     x3 = compute == "fp32_split3"
     fam = family_tags(patch, batch, bf16, x3)
     timed = set(fam) | {ops.WGRAD_GROUP_TAG}     # + the grouped launch of the other 5^3 filter gradients (bf16 storage)
-    full_table = bool(os.environ.get("BENCH_KERNEL_TABLE"))
+    full_table = args.full and bool(os.environ.get("BENCH_KERNEL_TABLE"))      # (per-launch table on stderr)
     graph = m._graph_mode() != "off"
     mode = m._graph_mode()
     # eager enqueue: HIP events go around the launches of the dominant kernel family only (an event packet idles the GPU
     # for ~5.6 us); graph replay: events cannot be timed inside a hipGraph on this runtime, the family is timed in eager
-    # steps right after the timed region
+    # steps right after the timed region.  Without --full no launch is timed.
+    events = args.full and not graph
     loss = None
-    if not graph:
+    if events:
         ops.profile_start(None if full_table else timed)
     nprep = 3 if graph else 0                # prepare: 2 eager steps + the capture (and first replay) of the step graph
     if mode == "segmented":
@@ -372,10 +405,10 @@ def measure(args, patch, batch, channels, classes, compute, rank, local, world):
     mode = m.step_mode()                     # (the autotune may have picked the eager enqueue)
     for _ in range(args.warmup):
         loss = m.train_step(images, labels)
-    if not graph:
+    if events:
         ops.profile_stop()                   # (synchronises; the warm-up records are dropped)
     barrier()
-    if not graph:
+    if events:
         ops.profile_start(None if full_table else timed)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -388,9 +421,12 @@ def measure(args, patch, batch, channels, classes, compute, rank, local, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = float(loss.detach())
+    if dump and rank == 0:
+        dump_outputs(dump, m, loss)
     nroof = min(args.steps, 10)
     fam_smi = None
-    if graph:
+    recs = []
+    if args.full and graph:
         m.force_eager = True                     # same kernels, enqueued one by one so that events can bracket them
         m.train_step(images, labels)
         barrier()
@@ -412,11 +448,11 @@ def measure(args, patch, batch, channels, classes, compute, rank, local, world):
                 torch.cuda.synchronize()
             th.join()
             fam_smi = box[0] if box else None
-    else:
+    elif events:
         recs = ops.profile_stop()
     barrier()
     sustained = None
-    if world == 1 and rank == 0 and not args.no_sustained:
+    if args.full and world == 1 and rank == 0 and not args.no_sustained:
         m.force_eager = False
         sustained = sustained_run(m, images, labels, dt / args.steps * 1e3)
 
@@ -477,7 +513,7 @@ def measure(args, patch, batch, channels, classes, compute, rank, local, world):
             "avg_ms": round(v[3] / v[0], 4), "tflops": round(v[1] / (v[3] * 1e-3) / 1e12, 1),
             "frac_of_peak": round(v[1] / (v[3] * 1e-3) / 1e12 / peak_for(bf16), 4), "launches_timed": v[0],
             "note": "incl. its split-K slab writes; the slabs' one batched reduce is a separate launch"}
-    if world == 1 and patch == 128 and not x3 and not os.environ.get("BENCH_NO_HBM_TABLE"):
+    if args.full and world == 1 and patch == 128 and not x3 and not os.environ.get("BENCH_NO_HBM_TABLE"):
         del m
         gc.collect()
         res["hbm_kernels"] = hbm_kernel_table(dev, bf16, classes)
@@ -562,7 +598,7 @@ def main():
         args.compute = "fp32_split3" if (promo and promo.get("promote")) else "fp32"
     promoted = args.compute == "fp32_split3" and not explicit        # the headline IS fp32_split3: the native step goes beside it
     bf16 = args.compute == "bf16"
-    r = measure(args, args.patch, args.batch, args.channels, args.classes, args.compute, rank, local, world)
+    r = measure(args, args.patch, args.batch, args.channels, args.classes, args.compute, rank, local, world, dump=args.dump_outputs)
     if rank == 0:
         P = args.patch
         metric = "training patches/sec (128^3x1ch fp32)" if not bf16 else \
@@ -595,14 +631,14 @@ def main():
         for k in ("conv_ms_per_step", "conv_tflops"):
             if k in r:
                 out[k] = r[k]
-    if world == 1 and args.compute in ("fp32", "fp32_split3") and not args.no_c5 and args.patch == 128 and args.channels == 1:
+    if args.full and world == 1 and args.compute in ("fp32", "fp32_split3") and not args.no_c5 and args.patch == 128 and args.channels == 1:
         # BASELINE configs[4] per-GPU workload on the same record (outside the headline's timed region)
         c5 = measure(args, args.patch, args.batch, 4, 5, "bf16", rank, local, world)
         c5["metric"] = "training patches/sec (128^3x4ch, 5 classes, bf16 storage + bf16 conv operands / fp32 accumulate, fp32 BN statistics and Dice sums), 1 GPU"
         c5["dtype"] = "bf16"
         c5["steps"], c5["warmup"] = args.steps, args.warmup
         out["c5_bf16"] = c5
-    if world == 1 and promoted and not args.no_x3 and args.patch == 128 and args.channels == 1:
+    if args.full and world == 1 and promoted and not args.no_x3 and args.patch == 128 and args.channels == 1:
         # promoted headline: the SAME step on the native fp32 MFMA kernels beside it, with its own roofline (VERDICT r5's ruling)
         nat = measure(args, args.patch, args.batch, args.channels, args.classes, "fp32", rank, local, world)
         out["c3_f32_native"] = {"metric": "training patches/sec (128^3x1ch fp32, v_mfma_f32_16x16x4_f32 kernels), 1 GPU", "dtype": "f32",
@@ -611,7 +647,7 @@ def main():
                                 "final_loss": nat["final_loss"], "step_enqueue": nat["step_enqueue"], "roofline": nat["roofline"],
                                 "sustained": nat.get("sustained")}
         out["hbm_kernels"], out["hbm_kernels_note"] = nat.get("hbm_kernels"), nat.get("hbm_kernels_note")
-    if world == 1 and args.compute == "fp32" and not args.no_x3 and args.patch == 128 and args.channels == 1:
+    if args.full and world == 1 and args.compute == "fp32" and not args.no_x3 and args.patch == 128 and args.channels == 1:
         # native headline: the same workload with ComputeDtype fp32_split3 NEXT TO it
         x3r = measure(args, args.patch, args.batch, args.channels, args.classes, "fp32_split3", rank, local, world)
         out["c3_f32x3"] = {"metric": "training patches/sec (128^3x1ch, fp32 tensors; 5^3 convolutions of the levels >= 32^3 as six bf16 MFMA "
@@ -624,14 +660,14 @@ def main():
                                      "f32x3 error 0.29-1.11 x, profiles/r06_x3_adversarial.txt; +-Inf / |x| >= 3.39e38 -> NaN) and "
                                      "tests/test_hip_golden_full.py::test_full_size_network_fp32 (both fp32 modes at ONE set of bounds from a "
                                      "ten-draw seed spread, profiles/r06_golden_seed_spread.txt)"}
-    if world == 1 and not bf16 and not args.no_c2 and args.patch == 128 and args.channels == 1:
+    if args.full and world == 1 and not bf16 and not args.no_c2 and args.patch == 128 and args.channels == 1:
         # BASELINE configs[1]: 64^3 patch, 1 modality, 2 classes, batch 2, fp32 -- the same measurement on a second model
         c2 = measure(args, 64, 2, 1, 2, "fp32", rank, local, world)
         out["c2_64cube_b2"] = {"metric": "training patches/sec (64^3x1ch fp32, batch 2), 1 GPU (BASELINE configs[1])", "value": c2["value"], "unit": "patches/s",
                                "ms_per_step": c2["ms_per_step"], "batch": 2, "patch": 64, "dtype": "f32", "steps": args.steps, "warmup": args.warmup,
                                "final_loss": c2["final_loss"], "step_enqueue": c2["step_enqueue"]}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         out["summary"] = summary(out)            # LAST key: survives a tail-truncated log (VERDICT r5 #7a)
         print(json.dumps(out))

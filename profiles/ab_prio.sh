@@ -12,6 +12,6 @@ for rep in 1 2 3; do
       VNET_HIP_LIB=$lib timeout 120 python profiles/bench_one.py $spec 50 2>&1 | tail -1
     done
     printf "%-24s C5 step " "$n"
-    VNET_HIP_LIB=$lib timeout 300 python bench.py --compute bf16 --channels 4 --classes 5 --no-cpu-baseline --no-sustained --no-c5 --no-c2 --no-x3 --steps 30 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['roofline']['frac'], d['roofline']['per_launch_ms'])"
+    VNET_HIP_LIB=$lib timeout 300 python bench.py --full --compute bf16 --channels 4 --classes 5 --no-cpu-baseline --no-sustained --no-c5 --no-c2 --no-x3 --steps 30 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['roofline']['frac'], d['roofline']['per_launch_ms'])"
   done
 done

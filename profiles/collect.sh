@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collects the evidence of one round on the GPU box (run through gpurun):
 #   bash profiles/collect.sh <outdir under gpurun_out>
-# 1. the bench line exactly as the driver runs it (incl. c3_f32x3, c5_bf16, c2_64cube_b2 and cpu_baseline),
+# 1. the bench line with --full (incl. c3_f32x3, c5_bf16, c2_64cube_b2 and cpu_baseline),
 # 2. rocprofv3 --kernel-trace --stats ONE LEG PER RUN (round 5, VERDICT r4 #5: the persistent-grid kernels have one grid whatever the
 #    problem, so a run that mixes the 128^3 headline with the 64^3 B=2 leg averaged two shapes into one row): fp32 headline only,
 #    fp32_split3 only, C5 (bf16) only, configs[1] (64^3, B=2) only -> <leg>_kernel_stats.csv,
@@ -13,8 +13,8 @@
 OUT=gpurun_out/${1:-prof}; shift || true
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p $OUT
-[ -n "$LEGS" ] || timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench.err
-COMMON="--no-cpu-baseline --no-sustained --no-c5 --no-c2 --no-x3"
+[ -n "$LEGS" ] || timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench.err
+COMMON="--full --no-cpu-baseline --no-sustained --no-c5 --no-c2 --no-x3"
 leg_args() {
   case $1 in
     fp32) echo "--gpus 1 --compute fp32 $COMMON" ;;

@@ -324,3 +324,28 @@ def test_step_without_gradient_memset_never_reads_stale_gradients(dev, monkeypat
     flat.begin_step()
     (p * 3.0).sum().backward()
     assert torch.equal(p.grad, torch.full((8,), 3.0, device=dev))      # cleared first: not 5
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(dev, tmp_path):
+    """`bench.py --dump-outputs DIR` without --full: the headline step alone (none of the --full legs on the line), and DIR holds
+    the last timed step's loss -- the one on the line -- and fixed samples of the parameters and gradients, float32, <= 64 MB."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--patch", "32", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert out["roofline"] is None and out["sustained"] is None and out["hbm_kernels"] is None
+    assert not {"c5_bf16", "c3_f32_native", "c3_f32x3", "c2_64cube_b2", "cpu_baseline"} & set(out)
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(got) == ["grads", "loss", "params"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["loss"].shape == (1,) and abs(float(got["loss"][0]) - out["final_loss"]) < 1e-6
+    assert got["params"].shape == got["grads"].shape == (1 << 22,) and np.abs(got["grads"]).max() > 0
