@@ -23,8 +23,10 @@ def bench(P, c0, c1, co, deep):
     wp = ops.packed_weights(w, ops.PACK_FWD_BF16, 125, c0 + c1, co)
     y = torch.empty(1, P, P, P, co, device=dev, dtype=torch.bfloat16)
 
+    r = ops.route(ops.FWD, 5, 1, 0, True, False, c0, c1, co, 1, (P, P, P), (P, P, P))
+
     def run():
-        ops._conv5_b16_call(x0, x1, wp, b, y, None, (P, P, P))
+        ops._conv_launch(r, x0, x1, w, b, y, wp=wp)
     for _ in range(5):
         run()
     torch.cuda.synchronize()

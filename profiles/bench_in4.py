@@ -32,7 +32,8 @@ for rep in range(2):
     for on in (False, True):
         ops._IN4["on"] = on
         with torch.no_grad():
-            ms = timed(lambda: ops._ConvFn.apply(x, None, w, b, 5, 1, False, None))
+            ms = timed(lambda: ops.conv(x, w, b, 5, 1))
         print("forward  x-im2col=%-5s %.3f ms" % (on, ms))
-    ms = timed(lambda: ops._wgrad5_b16_call(x, None, dy, dw, (P, P, P), 4))
+    wr = ops.route(ops.WGRAD, 5, 1, 0, True, False, x.shape[-1], 0, dy.shape[-1], 1, (P, P, P), (P, P, P), True, 4)
+    ms = timed(lambda: ops._wgrad_launch(wr, x, None, dy, dw))
     print("filter gradient          %.3f ms" % ms)

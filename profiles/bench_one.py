@@ -24,16 +24,16 @@ if mode == 'bf16':
     x, dy = x.to(torch.bfloat16), dy.to(torch.bfloat16)
 
 
+ops._X3["force"] = True                    # fp32_split3: the f32x3 filter gradient wherever it can run
+wr = ops.route(ops.WGRAD, 5, 1, 0, mode == 'bf16', mode == 'fp32_split3', x.shape[-1], 0, co, 1, (P, P, P), (P, P, P), True, ci)
+
+
 def run():
     if kind == 'conv':
         with torch.no_grad():
-            ops._ConvFn.apply(x, None, w, b, 5, 1, False, None)
-    elif mode == 'bf16':
-        ops._wgrad5_b16_call(x, None, dy, dw, (P, P, P), ci)
-    elif mode == 'fp32_split3':
-        ops._wgrad_x3_call(x, None, dy, dw, (P, P, P))
+            ops.conv(x, w, b, 5, 1)
     else:
-        ops._wgrad_call(5, 1, x, None, dy, dw, (P, P, P), (P, P, P))
+        ops._wgrad_launch(wr, x, None, dy, dw)
 
 
 for _ in range(3):

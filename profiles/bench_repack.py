@@ -1,6 +1,5 @@
 """Time of the one-launch filter repack (ops.repack_registered: every registered filter image of the network, after each optimiser
-step) for the bench network:  python profiles/bench_repack.py [fp32|fp32_split3|bf16] [reps]     (VNET_PACK_BOTH_X3=0: the f32x3 images
-one at a time, the round-5 form)"""
+step) for the bench network:  python profiles/bench_repack.py [fp32|fp32_split3|bf16] [reps]"""
 import sys
 import numpy as np
 import torch

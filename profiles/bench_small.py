@@ -19,7 +19,8 @@ for B, P, ci, co in SHAPES:
     res, ref = [], None
     for mode in (0, 1, 2):
         _lib.set_option("F32_SMALL", mode)
-        f = lambda: ops._conv_call(5, 1, 0, x, None, wp, None, y, None, (P, P, P), (P, P, P))
+        r = ops.route(ops.FWD, 5, 1, 0, False, False, ci, 0, co, B, (P, P, P), (P, P, P))
+        f = lambda: ops._conv_launch(r, x, None, w, None, y, wp=wp)
         for _ in range(5):
             f()
         torch.cuda.synchronize()

@@ -36,12 +36,17 @@ def tensors(P, c0, c1, co):
     return x0, x1, dy, dw
 
 
+def wgrad(x0, x1, dy, dw, owner=None):
+    P, c0, c1, co = x0.shape[1], x0.shape[-1], (x1.shape[-1] if x1 is not None else 0), dy.shape[-1]
+    ops._wgrad_launch(ops.route(ops.WGRAD, 5, 1, 0, True, False, c0, c1, co, 1, (P, P, P), (P, P, P), True, c0 + c1), x0, x1, dy, dw, owner)
+
+
 for (P, c0, c1, co) in SHAPES:
     x0, x1, dy, dw = tensors(P, c0, c1, co)
     out = []
     for zs in ("0", "1"):
         _lib.set_option("WGRAD_ZS", int(zs))
-        out.append(timeit(lambda: ops._wgrad5_b16_call(x0, x1, dy, dw, (P, P, P), c0 + c1)))
+        out.append(timeit(lambda: wgrad(x0, x1, dy, dw)))
     _lib.set_option("WGRAD_ZS", 2)
     fl = 2.0 * P ** 3 * 125 * (c0 + c1) * co
     print("wgrad-b16 %2d^3 %3d->%3d   round-3 kernel %6.1f us %7.1f TF/s   z-streaming %6.1f us %7.1f TF/s   x%.2f" % (
@@ -57,7 +62,7 @@ fl = sum(2.0 * P ** 3 * 125 * (c0 + c1) * co for (P, c0, c1, co) in LAYERS)
 def group():
     with ops.deferred_wgrad_reduce():
         for (P, c0, c1, co), (x0, x1, dy, dw), s in zip(LAYERS, ts, sinks):
-            ops._wgrad5_b16_call(x0, x1, dy, dw, (P, P, P), c0 + c1, owner=s)
+            wgrad(x0, x1, dy, dw, owner=s)
 
 
 for label, env in (("every layer on its own (round 3)", {"VNET_WGRAD_GROUP": "0"}),

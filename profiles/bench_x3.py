@@ -5,6 +5,8 @@ import torch
 sys.path.insert(0, ".")
 from vnet_tensorflow_amd import ops
 
+ops._X3["force"] = True          # fp32_split3 legs: the f32x3 kernels wherever they can run
+
 dev = torch.device("cuda", 0)
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 shapes = [tuple(int(v) for v in a.split(",")) for a in sys.argv[2:]] or [(128, 32, 16), (128, 16, 32), (128, 16, 16), (64, 32, 32), (64, 64, 32), (64, 32, 64), (32, 64, 64), (32, 128, 64), (32, 64, 128)]
@@ -18,10 +20,12 @@ for P, ci, co in shapes:
         ops.set_compute_dtype(mode)
         if mode == "fp32":
             wp = ops.packed_weights(w, ops.PACK_FWD, 125, ci, co)
-            f = lambda: ops._conv_call(5, 1, 0, x, None, wp, None, y, None, (P, P, P), (P, P, P))
+            r = ops.route(ops.FWD, 5, 1, 0, False, False, ci, 0, co, 1, (P, P, P), (P, P, P))
+            f = lambda: ops._conv_launch(r, x, None, w, None, y, wp=wp)
         else:
             wp = ops.packed_weights(w, ops.PACK_FWD_X3, 125, ci, co)
-            f = lambda: ops._conv_x3_call(x, None, wp, None, y, None, (P, P, P))
+            r = ops.route(ops.FWD, 5, 1, 0, False, True, ci, 0, co, 1, (P, P, P), (P, P, P))
+            f = lambda: ops._conv_launch(r, x, None, w, None, y, wp=wp)
         for _ in range(3):
             f()
         torch.cuda.synchronize()
@@ -41,7 +45,8 @@ for P, ci, co in shapes:
     outw = []
     for mode in ("fp32", "fp32_split3"):
         ops.set_compute_dtype(mode)
-        f = (lambda: ops._wgrad_call(5, 1, x, None, dy, dw, (P, P, P), (P, P, P))) if mode == "fp32" else (lambda: ops._wgrad_x3_call(x, None, dy, dw, (P, P, P)))
+        wr = ops.route(ops.WGRAD, 5, 1, 0, False, mode == "fp32_split3", ci, 0, co, 1, (P, P, P), (P, P, P), True, ci)
+        f = lambda: ops._wgrad_launch(wr, x, None, dy, dw)
         for _ in range(3):
             f()
         torch.cuda.synchronize()

@@ -26,6 +26,7 @@ else:
 w = (torch.randn(5, 5, 5, ci, co, generator=gen) * 0.05).to(dev)
 b = torch.randn(co, generator=gen).to(dev)
 wp = ops.packed_weights(w, ops.PACK_FWD_BF16, 125, ci, co)
+r = ops.route(ops.FWD, 5, 1, 0, True, False, x0.shape[-1], x1.shape[-1] if x1 is not None else 0, co, 1, shp[1:], shp[1:])
 y = torch.empty(*shp, co, device=dev, dtype=torch.bfloat16)
 stats = None
 if want_stats:
@@ -36,12 +37,12 @@ fn = L.vnet_debug_set_stamps
 fn.argtypes = [ctypes.c_void_p]
 assert fn(dbg.data_ptr()) == 0
 for _ in range(3):
-    ops._conv5_b16_call(x0, x1, wp, b, y, None, shp[1:], stats=stats)
+    ops._conv_launch(r, x0, x1, w, b, y, stats=stats, wp=wp)
 torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record()
 for _ in range(10):
-    ops._conv5_b16_call(x0, x1, wp, b, y, None, shp[1:], stats=stats)
+    ops._conv_launch(r, x0, x1, w, b, y, stats=stats, wp=wp)
 e1.record()
 torch.cuda.synchronize()
 print("%s %d->%d%s  %.3f ms per launch" % (kind, ci, co, " +stats" if want_stats else "", e0.elapsed_time(e1) / 10))

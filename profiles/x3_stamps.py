@@ -17,8 +17,10 @@ x = torch.randn(1, P, P, P, ci, device=dev)
 w = torch.randn(5, 5, 5, ci, co, device=dev) * 0.05
 y = torch.empty(1, P, P, P, co, device=dev)
 wp = ops.packed_weights(w, ops.PACK_FWD_X3, 125, ci, co)
+ops._X3["force"] = True
+r = ops.route(ops.FWD, 5, 1, 0, False, True, ci, 0, co, 1, (P, P, P), (P, P, P))
 for _ in range(3):
-    ops._conv_x3_call(x, None, wp, None, y, None, (P, P, P))
+    ops._conv_launch(r, x, None, w, None, y, wp=wp)
 torch.cuda.synchronize()
 t = buf.cpu().numpy().reshape(4, 8, 12)
 names = ["A+issue+P1", "P2", "P3(y)", "P4(col 4)", "barrier", "reduce+epilogue", "commit", "barrier"]

@@ -5,6 +5,7 @@ forward and backward computation below is a call into the HIP library on the cur
 There is no CPU or eager-PyTorch fallback -- non-GPU tensors raise (meta tensors are accepted
 for shape inference only, so a network can create its variables before the first batch).
 """
+import collections
 import contextlib
 import ctypes
 import math
@@ -272,9 +273,6 @@ def packed_weights(w, mode, taps, I, O):
     return wp
 
 
-_PACK_BOTH = {"on": True}      # (tests / A-B scripts flip the entry)
-
-
 def repack_registered():
     """After an optimiser step: refresh the packed copy of every registered filter in ONE kernel launch
     (instead of ~58 small launches spread over the next forward/backward pass)."""
@@ -299,12 +297,9 @@ def repack_registered():
         both = {}
         fams = {PACK_FWD_BF16: 0, PACK_BWD_BF16: 0, PACK_FWD: 1, PACK_BWD: 1,       # (the plain fp32 pair the same way: VNET_PACK_BOTH;
                 PACK_FWD_X3: 2, PACK_BWD_X3: 2}                                    #  the f32x3 pair: VNET_PACK_BOTH_X3, round 6)
-        if _os.environ.get("VNET_PACK_BOTH_X3", "1") == "0":
-            fams.pop(PACK_FWD_X3); fams.pop(PACK_BWD_X3)
-        if _PACK_BOTH["on"]:
-            for w, (mode, taps, I, O), wp in ents:
-                if mode in fams and I % 32 == 0 and O % 32 == 0:
-                    both.setdefault((w.data_ptr(), fams[mode]), {})[mode] = wp
+        for w, (mode, taps, I, O), wp in ents:
+            if mode in fams and I % 32 == 0 and O % 32 == 0:
+                both.setdefault((w.data_ptr(), fams[mode]), {})[mode] = wp
         done = set()
         for w, (mode, taps, I, O), wp in ents:
             key = (w.data_ptr(), fams.get(mode))
@@ -399,10 +394,6 @@ def _timed_tag(tag):
     return _PROFILE["on"] and (_PROFILE["only"] is None or tag in _PROFILE["only"])
 
 
-def _wgrad_tag(bf16, ks, kx, stride, wo, B, cin, co):
-    return "wgrad%s k%d%s s%d %d^3x%d %d->%d" % ("-bf16" if bf16 else "", ks, "x%d" % kx if kx else "", stride, wo, B, cin, co)
-
-
 class _Timed(object):
     """HIP events around one launch.  Not under stream capture: on this runtime (ROCm 7.0 libamdhip64 bundled with torch
     2.10) an event recorded into a capture cannot be timed afterwards -- hipEventRecordWithFlags(hipEventRecordExternal)
@@ -426,182 +417,151 @@ class _Timed(object):
             _PROFILE["records"].append(self.rec + (self.e0, self.e1))
 
 
-# ---- convolution family ----------------------------------------------------------------------------
-def _conv_call(ks, stride, up, x0, x1, wp, bias, y0, y1, dims_in, dims_out, kx=0, accum=False, stats=None, res=None):
-    L = _lib.lib()
-    B = x0.shape[0]
-    C0, C1 = x0.shape[-1], (x1.shape[-1] if x1 is not None else 0)
-    Cy0, Cy1 = y0.shape[-1], (y1.shape[-1] if y1 is not None else 0)
-    nb = L.vnet_conv_ws_bytes(ks, kx, stride, up, C0 + C1, Cy0 + Cy1, B, *dims_out)
-    ws = workspace(nb, x0.device) if nb else None
-    nin, nout = B * dims_in[0] * dims_in[1] * dims_in[2], B * dims_out[0] * dims_out[1] * dims_out[2]
-    taps = 8 if up else ks * ks * (kx or ks)
-    mac_vox = nin if up else nout          # the transposed conv does its 8 taps per INPUT voxel
-    flops = 2.0 * mac_vox * taps * (C0 + C1) * (Cy0 + Cy1)
-    nbytes = 4.0 * (nin * (C0 + C1) + nout * (Cy0 + Cy1) + taps * (C0 + C1) * (Cy0 + Cy1) + (Cy0 + Cy1))
-    tag = "conv k%d%s s%d%s %d^3x%d %d->%d" % (ks, "x%d" % kx if kx else "", stride, " up" if up else "", dims_out[2], B, C0 + C1, Cy0 + Cy1)
-    with _Timed(tag, flops, nbytes):
-        if stats is not None:        # batch-norm statistics of y (+ res) from the epilogue
-            check(L.vnet_conv_fwd_stats(ks, kx, stride, _ptr(x0), C0, _ptr(x1), C1, _ptr(wp), _ptr(bias), _ptr(y0), Cy0,
-                                        B, *dims_in, *dims_out, _ptr(res), _ptr(stats), _ptr(ws), nb, _stream()), "vnet_conv_fwd_stats")
-            return
-        fn = L.vnet_conv_fwd_acc if accum else L.vnet_conv_fwd
-        check(fn(ks, kx, stride, up, _ptr(x0), C0, _ptr(x1), C1, _ptr(wp), _ptr(bias),
-                 _ptr(y0), Cy0, _ptr(y1), Cy1, B, *dims_in, *dims_out,
-                 _ptr(ws), nb, _stream()), "vnet_conv_fwd")
-
-
-# force: (tests) take the f32x3 kernels for every shape they can run, not only where they pay;  ksplit: the deep levels (few bricks:
-# channel chunks split over workgroups, partial slabs + reduce) take them too (`_X3["ksplit"] = False`: A/B measurements)
-_X3 = {"force": False, "ksplit": True}
-
-
-def _x3_ok(C0, C1, Cy0, Cy1, B, dims):
-    if not _COMPUTE.get("split3"):
-        return False
-    if _X3["force"]:
-        return C0 % 16 == 0 and C1 % 16 == 0 and Cy0 % 16 == 0 and Cy1 % 16 == 0
-    L = _lib.lib()
-    if L.vnet_conv_x3_ok(C0, C1, Cy0, Cy1, B, *dims) != 1:
-        return False
-    return _X3["ksplit"] or L.vnet_conv_x3_ws_bytes(C0 + C1, Cy0 + Cy1, B, *dims) == 0
-
-
-def _conv_x3_call(x0, x1, wp, bias, y0, y1, dims, accum=False, stats=None, res=None):
-    """5^3 stride-1 conv, fp32 in / out, products from three-way split bf16 operands (vnet_conv_fwd_x3)."""
-    L = _lib.lib()
-    B = x0.shape[0]
-    C0, C1 = x0.shape[-1], (x1.shape[-1] if x1 is not None else 0)
-    Cy0, Cy1 = y0.shape[-1], (y1.shape[-1] if y1 is not None else 0)
-    nvox = B * dims[0] * dims[1] * dims[2]
-    flops = 2.0 * nvox * 125 * (C0 + C1) * (Cy0 + Cy1)
-    nbytes = 4.0 * (nvox * (C0 + C1) + nvox * (Cy0 + Cy1) + 125 * (C0 + C1) * (Cy0 + Cy1) + (Cy0 + Cy1))
-    tag = "conv-x3 k5 s1 %d^3x%d %d->%d" % (dims[2], B, C0 + C1, Cy0 + Cy1)
-    nb = L.vnet_conv_x3_ws_bytes(C0 + C1, Cy0 + Cy1, B, *dims)
-    ws = workspace(nb, x0.device) if nb else None
-    with _Timed(tag, flops, nbytes):
-        check(L.vnet_conv_fwd_x3(_ptr(x0), C0, _ptr(x1), C1, _ptr(wp), _ptr(bias), _ptr(y0), Cy0, _ptr(y1), Cy1, B, *dims,
-                                 _ptr(y0) if accum else None, _ptr(res), _ptr(stats), _ptr(ws), nb, _stream()), "vnet_conv_fwd_x3")
-
-
-# ---- bf16-storage convolution calls (include/vnet_hip.h: vnet_conv_fwd_b16, vnet_conv2_fwd_b16, ...) ----------------------------
+# ---- convolution routing ---------------------------------------------------------------------------
+# Every launch of the convolution family -- forward, backward-data and filter gradient of _ConvFn, the fused input block -- is chosen
+# by route() and only there: the statistics buffer a forward needs, the side-stream guard of a filter gradient and the launch itself
+# all read the one record it returns.
+FWD, BWD, WGRAD, IN_FWD, IN_WGRAD = "fwd", "bwd", "wgrad", "input-fwd", "input-wgrad"
+# (tests / A-B runs; read by route() alone)  _X3 force: the f32x3 kernels for every shape they can run, not only where they pay;
+# _IN4: the zero-padded bf16 network input through vnet_conv_fwd_b16_padded;  _DIRECT2: False = the generic 2^3 kernels everywhere
+_X3 = {"force": False}
 _IN4 = {"on": True}
+_DIRECT2 = {"on": True}
 
 
-def _conv5_b16_call(x0, x1, wp, bias, y0, y1, dims, accum=False, stats=None, res=None, acc_src=None, cin_real=0):
-    """cin_real: the input channels of the FILTER when x0 carries zero-padded channels behind them (the cast network input)."""
+class Route(collections.namedtuple("Route", "family pack ws stats_rows tag flops nbytes ks kx stride up din dout cin")):
+    """One launch as route() chose it.  family: the entry point; pack: (mode, taps, I, O) of the packed filter, None = the raw
+    filter; ws: workspace bytes; stats_rows: partial batch-norm rows the forward's epilogue writes (0 = none); tag, flops, nbytes:
+    the profile record.  Geometry of the launch: x [B, din, .] -> y [B, dout, .] (a filter gradient: x and dy [B, dout, .]) -- for
+    a backward-data launch the forward's input and output swap roles; cin: the filter's input channels."""
+    __slots__ = ()
+
+
+def _nvox(dims):
+    return dims[0] * dims[1] * dims[2]
+
+
+def route(op, ks, stride, up, bf16, split3, C0, C1, O, B, din, dout, aligned=True, cin=0, res=False):
+    """The launch for `op` of the convolution y [B, dout, O] = conv(x [B, din, C0 | C1]): ks^3 stride `stride`, or (up) the 2^3
+    transposed convolution.  bf16: bf16 storage; split3: the fp32_split3 mode; aligned: the filter is 16-byte aligned; cin: the
+    filter's input channels when x carries zero-padded channels behind them (the cast network input); res: a residual joins the
+    epilogue statistics.  IN_FWD / IN_WGRAD: the fused 1-channel input block (C0 = 1, O outputs, din = dout)."""
     L = _lib.lib()
-    B = x0.shape[0]
-    C0, C1 = x0.shape[-1], (x1.shape[-1] if x1 is not None else 0)
-    Cy0, Cy1 = y0.shape[-1], (y1.shape[-1] if y1 is not None else 0)
-    nb = L.vnet_conv_b16_ws_bytes(C0, C1, Cy0, Cy1, B, *dims)
-    ws = workspace(nb, x0.device) if nb else None
-    nvox = B * dims[0] * dims[1] * dims[2]
-    flops = 2.0 * nvox * 125 * (C0 + C1) * (Cy0 + Cy1)
-    nbytes = 2.0 * nvox * (C0 + C1 + Cy0 + Cy1) + 2.0 * 125 * (C0 + C1) * (Cy0 + Cy1)
-    tag = "conv-bf16 k5 s1 %d^3x%d %d->%d" % (dims[2], B, C0 + C1, Cy0 + Cy1)
-    acc = _ptr(acc_src) if acc_src is not None else (_ptr(y0) if accum else None)
-    with _Timed(tag, flops, nbytes):
-        if cin_real and _IN4["on"] and x1 is None and y1 is None and not accum and acc_src is None:
-            check(L.vnet_conv_fwd_b16_padded(_ptr(x0), C0, int(cin_real), _ptr(wp), _ptr(bias), _ptr(y0), Cy0, B, *dims,
-                                             _ptr(res), _ptr(stats), _ptr(ws), nb, _stream()), "vnet_conv_fwd_b16_padded")
-            return
-        check(L.vnet_conv_fwd_b16(_ptr(x0), C0, _ptr(x1), C1, _ptr(wp), _ptr(bias), _ptr(y0), Cy0, _ptr(y1), Cy1, B, *dims,
-                                  acc, _ptr(res), _ptr(stats), _ptr(ws), nb, _stream()), "vnet_conv_fwd_b16")
-
-
-def _wgrad5_b16_call(x0, x1, dy, dw, dims, cin_dw, owner=None):
-    L = _lib.lib()
-    B = x0.shape[0]
-    C0, C1 = x0.shape[-1], (x1.shape[-1] if x1 is not None else 0)
-    Co = dy.shape[-1]
-    nb = L.vnet_wgrad_bf16_ws_bytes(C0 + C1, Co, B, *dims)
-    ws = _wgrad_workspace(dw, nb, False, owner)
-    nvox = B * dims[0] * dims[1] * dims[2]
-    flops = 2.0 * nvox * 125 * (C0 + C1) * Co
-    nbytes = 2.0 * nvox * (C0 + C1 + Co) + 4.0 * 125 * (C0 + C1) * Co
-    tag = _wgrad_tag(True, 5, 0, 1, dims[2], B, C0 + C1, Co)
-    if (_DEFER["on"] and owner is not None and _GROUP["on"] and not _timed_tag(tag) and _LAUNCH_ON[0] is None
-            and dims[0] * dims[1] * dims[2] <= _GROUP["max_voxels"] and not (cin_dw <= 4 and C0 == 8 and C1 == 0)):
-        # a deep-level layer of a pass whose filter gradients nobody reads before it ends: launched together with the others when the
-        # pass ends (vnet_conv_wgrad_b16_group); the tensors stay alive -- and unmodified, see _ConvFn.backward -- until then
-        _DEFER["jobs"].append((x0, x1, dy, dw, ws, nb, int(cin_dw), B, tuple(dims), flops, nbytes, 5))
-        _DEFER["dy_ptrs"].add(dy.data_ptr())
-        _group_pinned(x0, x1, dy)
-        return
-    with _Timed(tag, flops, nbytes), _immediate_reduce(owner is None):
-        check(L.vnet_conv_wgrad_b16(_ptr(x0), C0, _ptr(x1), C1, _ptr(dy), Co, _ptr(dw), int(cin_dw), B, *dims, _ptr(ws), nb, _stream()),
-              "vnet_conv_wgrad_b16")
-
-
-def _conv2_b16_call(up, x, wp, bias, y, dims_in, dims_out, accum=False, stats=None):
-    L = _lib.lib()
-    B, Cin, Cout = x.shape[0], x.shape[-1], y.shape[-1]
-    nb = L.vnet_conv_ws_bytes(2, 0, 2, up, Cin, Cout, B, *dims_out)
-    ws = workspace(nb, x.device) if nb else None
-    nin, nout = B * dims_in[0] * dims_in[1] * dims_in[2], B * dims_out[0] * dims_out[1] * dims_out[2]
-    flops = 2.0 * (nin if up else nout) * 8 * Cin * Cout
-    nbytes = 2.0 * (nin * Cin + nout * Cout) + 4.0 * 8 * Cin * Cout
-    tag = "conv-b16 k2 s2%s %d^3x%d %d->%d" % (" up" if up else "", dims_out[2], B, Cin, Cout)
-    with _Timed(tag, flops, nbytes):
-        check(L.vnet_conv2_fwd_b16(int(up), _ptr(x), Cin, _ptr(wp), _ptr(bias), _ptr(y), Cout, B, *dims_in, *dims_out,
-                                   int(bool(accum)), _ptr(stats), _ptr(ws), nb, _stream()), "vnet_conv2_fwd_b16")
-
-
-_DIRECT2 = {"on": True}          # (tests / A-B: False = always the generic kernels)
-
-
-def _conv2_b16(down, x, w, bias, y, dims_fine, dims_coarse, Cf, Cc, accum=False, stats=None):
-    """The 2^3 stride-2 pair (fp32 or bf16 tensors, by the dtype of x).  down: coarse y = conv(fine x); else fine y (+)= transposed conv(coarse x).
-    w: the fp32 filter in TF layout -- [2,2,2,Cf,Cc] for BOTH layers2.down_convolution (Cin = Cf) and layers2.up_convolution
-    (filter [k,k,k,Cout = Cf,Cin = Cc]).  Levels 1-2 of the V-Net (Cf 16 / 32) take the LDS-free direct kernels
-    (csrc/conv2_b16.hip: one 16-byte load = one MFMA operand), other widths the generic fp32-MFMA kernels on packed weights."""
-    L = _lib.lib()
-    B = x.shape[0]
-    f32 = x.dtype == torch.float32
-    if _DIRECT2["on"] and L.vnet_conv2_direct_ok(Cf, Cc) and w.data_ptr() % 16 == 0:
-        nf = B * dims_fine[0] * dims_fine[1] * dims_fine[2]
-        nc = B * dims_coarse[0] * dims_coarse[1] * dims_coarse[2]
-        tag = "conv%s k2 s2%s %d^3x%d %d->%d" % ("" if f32 else "-b16", "" if down else " up", (dims_coarse if down else dims_fine)[2], B,
-                                                 Cf if down else Cc, Cc if down else Cf)
-        esz = 4.0 if f32 else 2.0
-        with _Timed(tag, 2.0 * nc * 8 * Cf * Cc, esz * (nf * Cf + nc * Cc) + 4.0 * 8 * Cf * Cc):
-            fn, what = (L.vnet_conv2_direct_f32, "vnet_conv2_direct_f32") if f32 else (L.vnet_conv2_direct_b16, "vnet_conv2_direct_b16")
-            check(fn(int(bool(down)), _ptr(x), _ptr(y), _ptr(w), _ptr(bias), Cf, Cc, B, *dims_fine, *dims_coarse,
-                     int(bool(accum)), _ptr(stats), _stream()), what)
-        return
-    if f32:             # the generic fp32 MFMA kernels on packed filters (any width)
-        if down:
-            _conv_call(2, 2, 0, x, None, packed_weights(w, PACK_FWD, 8, Cf, Cc), bias, y, None, dims_fine, dims_coarse, accum=accum, stats=stats)
+    din, dout = tuple(int(v) for v in din), tuple(int(v) for v in dout)
+    I, kx, esz = cin or C0 + C1, 0, (2 if bf16 else 4)
+    if op in (IN_FWD, IN_WGRAD):
+        N = B * _nvox(din)
+        if _FUSE["input_direct"] and L.vnet_input_conv_direct_ok(O, B, *din) == 1:
+            # packed fp32 FMAs straight from the image: no im2col tensor, no filter repack
+            fwd = op == IN_FWD
+            return Route("input-direct" if fwd else "input-wgrad-direct", None,
+                         0 if fwd else L.vnet_input_wgrad_direct_slabs(B, *din) * 25 * 16 * O * 4,
+                         L.vnet_input_conv_direct_stats_rows(B, *din) if fwd else 0,
+                         "%s %d^3x%d 1->%d" % ("input-direct" if fwd else "input-wgrad-direct", din[2], B, O),
+                         2.0 * N * 125 * O, 4.0 * N * (1 + O), 5, 0, 1, 0, din, dout, 1)
+        # rounds 1-5: the x-im2col tensor (16 channels) through the 5x5x1 fp32 MFMA kernels
+        op, kx, I, C0, C1 = (FWD if op == IN_FWD else WGRAD), 1, 16, 16, 0
+    taps = 8 if ks == 2 else ks * ks * (kx or ks)
+    if op == WGRAD:
+        if up:      # dw[a][o][ci] = sum_i dy[2i+a][o] * x[i][ci] == the filter gradient of the 2^3 down conv (fine dy -> coarse x)
+            C0, C1, O, din, dout, up = O, 0, C0, dout, din, 0
+        cx, nin, nout = C0 + C1, B * _nvox(din), B * _nvox(dout)
+        if bf16:
+            fam, pre = ("wgrad2-b16", "wgrad-b16") if ks == 2 else ("wgrad-bf16", "wgrad-bf16")
+        elif ks == 5 and stride == 1 and kx == 0 and split3 and (
+                (C0 % 16 == 0 and C1 % 16 == 0 and O % 16 == 0) if _X3["force"] else L.vnet_wgrad_x3_ok(C0, C1, O, B, *din) == 1):
+            fam = pre = "wgrad-x3"
         else:
-            _conv_call(2, 2, 1, x, None, packed_weights(w, PACK_UP, 8, Cc, Cf), bias, y, None, dims_coarse, dims_fine, accum=accum)
-        return
-    if down:
-        _conv2_b16_call(0, x, packed_weights(w, PACK_FWD | PACK_ROUND16, 8, Cf, Cc), bias, y, dims_fine, dims_coarse, accum=accum, stats=stats)
+            fam = pre = "wgrad"
+        ws = (L.vnet_wgrad_x3_ws_bytes(cx, O, B, *din) if fam == "wgrad-x3" else
+              L.vnet_wgrad_bf16_ws_bytes(cx, O, B, *din) if fam == "wgrad-bf16" else
+              L.vnet_wgrad_ws_bytes(ks, kx, stride, cx, O, B, *dout))
+        # (the 2^3 bf16 kernel counts the fine tensor as 8 voxels per coarse one)
+        nbytes = esz * ((8 * nout if fam == "wgrad2-b16" else nin) * cx + nout * O) + 4.0 * taps * cx * O
+        return Route(fam, None, ws, 0, "%s k%d%s s%d %d^3x%d %d->%d" % (pre, ks, "x%d" % kx if kx else "", stride, dout[2], B, cx, O),
+                     2.0 * nout * taps * cx * O, nbytes, ks, kx, stride, 0, din, dout, cx if ks == 2 else I)
+    pair = ks == 2 and (bf16 or op == BWD or (C1 == 0 and (up or not res)))       # the 2^3 stride-2 down / up pair
+    if op == BWD:   # backward-data: x = dy, y = dx; of a 2^3 layer the other member of the pair with the same filter
+        (X0, X1), (Y0, Y1), din, dout, up = (O, 0), (C0, C1), dout, din, (not up if ks == 2 else 0)
     else:
-        _conv2_b16_call(1, x, packed_weights(w, PACK_UP | PACK_ROUND16, 8, Cc, Cf), bias, y, dims_coarse, dims_fine, accum=accum)
+        (X0, X1), (Y0, Y1) = (C0, C1), (O, 0)
+    cx, cy, nin, nout, up = X0 + X1, Y0 + Y1, B * _nvox(din), B * _nvox(dout), int(up)
+    if pair:
+        Cf, Cc = (cy, cx) if up else (cx, cy)
+        if _DIRECT2["on"] and L.vnet_conv2_direct_ok(Cf, Cc) and aligned:
+            # levels 1-2 of the V-Net (Cf 16 / 32): the LDS-free direct kernels on the raw filter (one 16-byte load = one MFMA operand)
+            fam, pack = "conv2-direct", None
+        else:
+            fam, pack = ("conv2-b16" if bf16 else "conv"), ((PACK_UP if up else PACK_FWD) | (PACK_ROUND16 if bf16 else 0), 8, cx, cy)
+        pre = "conv-b16" if bf16 else "conv"
+    elif bf16:
+        fam = "conv-bf16-padded" if op == FWD and C1 == 0 and 0 < cin < C0 and _IN4["on"] else "conv-bf16"
+        pack, pre = (PACK_BWD_BF16 if op == BWD else PACK_FWD_BF16, 125, I, O), "conv-bf16"
+    elif ks == 5 and stride == 1 and not up and kx == 0 and split3 and (
+            (X0 % 16 == 0 and X1 % 16 == 0 and Y0 % 16 == 0 and Y1 % 16 == 0) if _X3["force"] else
+            L.vnet_conv_x3_ok(X0, X1, Y0, Y1, B, *dout) == 1):
+        fam = pre = "conv-x3"
+        pack = (PACK_BWD_X3 if op == BWD else PACK_FWD_X3, 125, I, O)
+    else:
+        fam = pre = "conv"
+        pack = ((PACK_UP, 8, cx, cy) if up else (PACK_BWD, taps, I, O) if op == BWD else (PACK_FWD, taps, I, O))
+    ws = (0 if fam == "conv2-direct" else
+          L.vnet_conv_x3_ws_bytes(cx, cy, B, *dout) if fam == "conv-x3" else
+          L.vnet_conv_b16_ws_bytes(X0, X1, Y0, Y1, B, *dout) if pre == "conv-bf16" else
+          L.vnet_conv_ws_bytes(ks, kx, stride, up, cx, cy, B, *dout))
+    rows = 0
+    if op == FWD and not up and not (bf16 and pair and O % 4):
+        if pre == "conv-bf16":
+            rows = L.vnet_conv_b16_stats_rows(C0, C1, O, 0, B, *dout)     # (the kernels that stage bf16 sources: one row per brick)
+        else:
+            rows = (L.vnet_conv_x3_stats_rows(cx, O, B, *dout) if fam == "conv-x3" else          # one row per brick or reduce block
+                    L.vnet_conv2_direct_stats_rows(cx, O, B, *dout) if fam == "conv2-direct" else 0)   # one row per workgroup
+            if rows <= 0:
+                rows = L.vnet_conv_stats_rows(ks, kx, stride, 0, cx, O, 0, B, *dout)    # the fp32 MFMA kernels' brick rows
+    nbytes = (esz * (nin * cx + nout * cy) + (2.0 if pre == "conv-bf16" else 4.0) * taps * cx * cy
+              + (4.0 * cy if fam in ("conv", "conv-x3") else 0))
+    return Route(fam, pack, ws, max(rows, 0),
+                 "%s k%d%s s%d%s %d^3x%d %d->%d" % (pre, ks, "x%d" % kx if kx else "", stride, " up" if up else "", dout[2], B, cx, cy),
+                 2.0 * (nin if up else nout) * taps * cx * cy, nbytes, ks, kx, stride, up, din, dout, I)
 
 
-def _wgrad2_b16_call(xfine, dycoarse, dw, dims_fine, dims_coarse, owner=None):
+def _conv_launch(r, x0, x1, w, bias, y0, y1=None, accum=False, stats=None, res=None, acc_src=None, wp=None):
+    """Run a FWD / BWD route: y0 | y1 (+)= conv(x0 | x1) (+ bias).  stats: the epilogue's partial sums of y (+ res); acc_src: the
+    bf16 kernel adds this tensor instead of y0; wp: the packed filter when the caller made it (default: w's cached image)."""
     L = _lib.lib()
-    immediate = owner is None
-    B, Cin, Co = xfine.shape[0], xfine.shape[-1], dycoarse.shape[-1]
-    nb = L.vnet_wgrad_ws_bytes(2, 0, 2, Cin, Co, B, *dims_coarse)
-    ws = _wgrad_workspace(dw, nb, immediate, owner)
-    nout = B * dims_coarse[0] * dims_coarse[1] * dims_coarse[2]
-    tag = "wgrad-b16 k2 s2 %d^3x%d %d->%d" % (dims_coarse[2], B, Cin, Co)
-    if (_DEFER["on"] and not immediate and _GROUP["on"] and _GROUP["k2"] and not _timed_tag(tag) and _LAUNCH_ON[0] is None
-            and tuple(dims_coarse) == tuple((d + 1) // 2 for d in dims_fine)
-            and dims_fine[0] * dims_fine[1] * dims_fine[2] <= _GROUP["max_voxels"]):
-        # joins the grouped launch of the pass's filter gradients (ks = 2: x = the fine tensor, dy = the coarse one)
-        _DEFER["jobs"].append((xfine, None, dycoarse, dw, ws, nb, int(Cin), B, tuple(dims_fine),
-                               2.0 * nout * 8 * Cin * Co, 2.0 * nout * (8 * Cin + Co) + 4.0 * 8 * Cin * Co, 2))
-        _DEFER["dy_ptrs"].add(dycoarse.data_ptr())
-        _group_pinned(xfine, None, dycoarse)
-        return
-    with _Timed(tag, 2.0 * nout * 8 * Cin * Co, 2.0 * nout * (8 * Cin + Co) + 4.0 * 8 * Cin * Co), _immediate_reduce(immediate):
-        check(L.vnet_conv2_wgrad_b16(_ptr(xfine), Cin, _ptr(dycoarse), Co, _ptr(dw), B, *dims_fine, *dims_coarse, _ptr(ws), nb, _stream()),
-              "vnet_conv2_wgrad_b16")
+    B, C0, C1 = x0.shape[0], x0.shape[-1], (x1.shape[-1] if x1 is not None else 0)
+    Cy0, Cy1 = y0.shape[-1], (y1.shape[-1] if y1 is not None else 0)
+    if wp is None:
+        wp = packed_weights(w, *r.pack) if r.pack is not None else w
+    nb, f = r.ws, r.family
+    ws = workspace(nb, x0.device) if nb else None
+    with _Timed(r.tag, r.flops, r.nbytes):
+        if f == "conv2-direct":
+            down = not r.up
+            fine, coarse, Cf, Cc = (r.din, r.dout, C0, Cy0) if down else (r.dout, r.din, Cy0, C0)
+            fn, what = (L.vnet_conv2_direct_b16, "vnet_conv2_direct_b16") if _is16(x0) else (L.vnet_conv2_direct_f32, "vnet_conv2_direct_f32")
+            check(fn(int(down), _ptr(x0), _ptr(y0), _ptr(wp), _ptr(bias), Cf, Cc, B, *fine, *coarse, int(bool(accum)), _ptr(stats),
+                     _stream()), what)
+        elif f == "conv2-b16":
+            check(L.vnet_conv2_fwd_b16(r.up, _ptr(x0), C0, _ptr(wp), _ptr(bias), _ptr(y0), Cy0, B, *r.din, *r.dout, int(bool(accum)),
+                                       _ptr(stats), _ptr(ws), nb, _stream()), "vnet_conv2_fwd_b16")
+        elif f == "conv-bf16-padded":
+            check(L.vnet_conv_fwd_b16_padded(_ptr(x0), C0, r.cin, _ptr(wp), _ptr(bias), _ptr(y0), Cy0, B, *r.dout,
+                                             _ptr(res), _ptr(stats), _ptr(ws), nb, _stream()), "vnet_conv_fwd_b16_padded")
+        elif f == "conv-bf16":
+            acc = acc_src if acc_src is not None else (y0 if accum else None)
+            check(L.vnet_conv_fwd_b16(_ptr(x0), C0, _ptr(x1), C1, _ptr(wp), _ptr(bias), _ptr(y0), Cy0, _ptr(y1), Cy1, B, *r.dout,
+                                      _ptr(acc), _ptr(res), _ptr(stats), _ptr(ws), nb, _stream()), "vnet_conv_fwd_b16")
+        elif f == "conv-x3":
+            check(L.vnet_conv_fwd_x3(_ptr(x0), C0, _ptr(x1), C1, _ptr(wp), _ptr(bias), _ptr(y0), Cy0, _ptr(y1), Cy1, B, *r.dout,
+                                     _ptr(y0) if accum else None, _ptr(res), _ptr(stats), _ptr(ws), nb, _stream()), "vnet_conv_fwd_x3")
+        elif stats is not None:        # the fp32 MFMA kernels with batch-norm statistics of y (+ res) from the epilogue
+            check(L.vnet_conv_fwd_stats(r.ks, r.kx, r.stride, _ptr(x0), C0, _ptr(x1), C1, _ptr(wp), _ptr(bias), _ptr(y0), Cy0,
+                                        B, *r.din, *r.dout, _ptr(res), _ptr(stats), _ptr(ws), nb, _stream()), "vnet_conv_fwd_stats")
+        else:
+            fn = L.vnet_conv_fwd_acc if accum else L.vnet_conv_fwd
+            check(fn(r.ks, r.kx, r.stride, r.up, _ptr(x0), C0, _ptr(x1), C1, _ptr(wp), _ptr(bias),
+                     _ptr(y0), Cy0, _ptr(y1), Cy1, B, *r.din, *r.dout, _ptr(ws), nb, _stream()), "vnet_conv_fwd")
 
 
 def cast_input(img):
@@ -740,47 +700,86 @@ def _immediate_reduce(immediate):
         L.vnet_wgrad_defer(1, st)
 
 
-def _wgrad_x3_ok(C0, C1, Co, B, dims):
-    if not _COMPUTE.get("split3"):
-        return False
-    if _X3["force"]:
-        return C0 % 16 == 0 and C1 % 16 == 0 and Co % 16 == 0
-    return _lib.lib().vnet_wgrad_x3_ok(C0, C1, Co, B, *dims) == 1
-
-
-def _wgrad_x3_call(x0, x1, dy, dw, dims, owner=None):
-    """Filter gradient of the 5^3 stride-1 conv, fp32 tensors, products from three-way split bf16 operands (vnet_conv_wgrad_x3)."""
+def _wgrad_launch(r, x0, x1, dy, dw, owner=None):
+    """Run a WGRAD route: dw = the filter gradient of x0 | x1 against dy.  owner: the parameter's gradient sink, whose buffer keeps
+    the partial slabs of a deferred reduce; None = a gradient consumed right away (reduced now even inside a deferring pass)."""
     L = _lib.lib()
-    B = x0.shape[0]
-    C0, C1 = x0.shape[-1], (x1.shape[-1] if x1 is not None else 0)
-    Co = dy.shape[-1]
-    nb = L.vnet_wgrad_x3_ws_bytes(C0 + C1, Co, B, *dims)
-    ws = _wgrad_workspace(dw, nb, owner is None, owner)
-    nvox = B * dims[0] * dims[1] * dims[2]
-    flops = 2.0 * nvox * 125 * (C0 + C1) * Co
-    nbytes = 4.0 * (nvox * (C0 + C1 + Co) + 125 * (C0 + C1) * Co)
-    tag = "wgrad-x3 k5 s1 %d^3x%d %d->%d" % (dims[2], B, C0 + C1, Co)
-    with _Timed(tag, flops, nbytes), _immediate_reduce(owner is None):
-        check(L.vnet_conv_wgrad_x3(_ptr(x0), C0, _ptr(x1), C1, _ptr(dy), Co, _ptr(dw), B, *dims, _ptr(ws), nb, _stream()),
-              "vnet_conv_wgrad_x3")
-
-
-def _wgrad_call(ks, stride, x0, x1, dy, dw, dims_in, dims_out, kx=0, immediate=False, owner=None):
-    L = _lib.lib()
-    immediate = immediate or owner is None          # no sink to keep the slabs on: reduce on the spot
-    B = x0.shape[0]
-    C0, C1 = x0.shape[-1], (x1.shape[-1] if x1 is not None else 0)
-    Co = dy.shape[-1]
-    nb = L.vnet_wgrad_ws_bytes(ks, kx, stride, C0 + C1, Co, B, *dims_out)
+    immediate = owner is None
+    B, C0, C1, Co = x0.shape[0], x0.shape[-1], (x1.shape[-1] if x1 is not None else 0), dy.shape[-1]
+    nb, f = r.ws, r.family
     ws = _wgrad_workspace(dw, nb, immediate, owner)
-    nin, nout = B * dims_in[0] * dims_in[1] * dims_in[2], B * dims_out[0] * dims_out[1] * dims_out[2]
-    taps = ks * ks * (kx or ks)
-    flops = 2.0 * nout * taps * (C0 + C1) * Co
-    nbytes = 4.0 * (nin * (C0 + C1) + nout * Co + taps * (C0 + C1) * Co)
-    tag = _wgrad_tag(False, ks, kx, stride, dims_out[2], B, C0 + C1, Co)
-    with _Timed(tag, flops, nbytes), _immediate_reduce(immediate):
-        check(L.vnet_conv_wgrad(ks, kx, stride, _ptr(x0), C0, _ptr(x1), C1, _ptr(dy), Co, _ptr(dw),
-                                B, *dims_in, *dims_out, _ptr(ws), nb, _stream()), "vnet_conv_wgrad")
+    if (f in ("wgrad-bf16", "wgrad2-b16") and _DEFER["on"] and not immediate and _GROUP["on"] and not _timed_tag(r.tag)
+            and _LAUNCH_ON[0] is None and _nvox(r.din) <= _GROUP["max_voxels"]
+            and (_GROUP["k2"] and r.dout == tuple((d + 1) // 2 for d in r.din) if r.ks == 2 else
+                 not (r.cin <= 4 and C0 == 8 and C1 == 0))):
+        # a deep-level layer of a pass whose filter gradients nobody reads before it ends: launched together with the others when the
+        # pass ends (vnet_conv_wgrad_b16_group; ks = 2: x = the fine tensor, dy = the coarse one); the tensors stay alive -- and
+        # unmodified, see _ConvFn.backward -- until then
+        _DEFER["jobs"].append((x0, x1, dy, dw, ws, nb, int(r.cin), B, r.din, r.flops, r.nbytes, r.ks))
+        _DEFER["dy_ptrs"].add(dy.data_ptr())
+        _group_pinned(x0, x1, dy)
+        return
+    with _Timed(r.tag, r.flops, r.nbytes), _immediate_reduce(immediate):
+        if f == "wgrad-x3":
+            check(L.vnet_conv_wgrad_x3(_ptr(x0), C0, _ptr(x1), C1, _ptr(dy), Co, _ptr(dw), B, *r.din, _ptr(ws), nb, _stream()),
+                  "vnet_conv_wgrad_x3")
+        elif f == "wgrad-bf16":
+            check(L.vnet_conv_wgrad_b16(_ptr(x0), C0, _ptr(x1), C1, _ptr(dy), Co, _ptr(dw), int(r.cin), B, *r.din, _ptr(ws), nb,
+                                        _stream()), "vnet_conv_wgrad_b16")
+        elif f == "wgrad2-b16":
+            check(L.vnet_conv2_wgrad_b16(_ptr(x0), C0, _ptr(dy), Co, _ptr(dw), B, *r.din, *r.dout, _ptr(ws), nb, _stream()),
+                  "vnet_conv2_wgrad_b16")
+        else:
+            check(L.vnet_conv_wgrad(r.ks, r.kx, r.stride, _ptr(x0), C0, _ptr(x1), C1, _ptr(dy), Co, _ptr(dw),
+                                    B, *r.din, *r.dout, _ptr(ws), nb, _stream()), "vnet_conv_wgrad")
+
+
+# ---- one family's launch on explicit tensors (tests and profile scripts reach a kernel through these) -------------------------
+# Each asks route() for the layer and refuses a shape the named family does not take: no quiet fall-back to another kernel.
+def _family(r, *families):
+    if r.family not in families:
+        raise VnetHipError("%s: routed to %s, not %s" % (r.tag, r.family, " / ".join(families)))
+    return r
+
+
+def _conv_x3_call(x0, x1, wp, bias, y0, y1, dims, accum=False, stats=None, res=None):
+    """5^3 stride-1 conv on the f32x3 kernels (vnet_conv_fwd_x3); wp: the PACK_FWD_X3 / PACK_BWD_X3 image; y1: a two-destination
+    (backward-data shaped) launch."""
+    C0, C1, Cy0, Cy1 = x0.shape[-1], (x1.shape[-1] if x1 is not None else 0), y0.shape[-1], (y1.shape[-1] if y1 is not None else 0)
+    op, (a0, a1, o) = (FWD, (C0, C1, Cy0)) if y1 is None else (BWD, (Cy0, Cy1, C0))
+    r = _family(route(op, 5, 1, 0, False, True, a0, a1, o, x0.shape[0], dims, dims), "conv-x3")
+    _conv_launch(r, x0, x1, None, bias, y0, y1, accum=accum, stats=stats, res=res, wp=wp)
+
+
+def _conv5_b16_call(x0, x1, wp, bias, y0, y1, dims, accum=False, stats=None, res=None, acc_src=None, cin_real=0):
+    """5^3 stride-1 conv on bf16 tensors (vnet_conv_fwd_b16; vnet_conv_fwd_b16_padded for an input whose filter has cin_real < C0
+    channels); wp: the PACK_FWD_BF16 / PACK_BWD_BF16 image."""
+    C0, C1, Cy0, Cy1 = x0.shape[-1], (x1.shape[-1] if x1 is not None else 0), y0.shape[-1], (y1.shape[-1] if y1 is not None else 0)
+    op, (a0, a1, o) = (FWD, (C0, C1, Cy0)) if y1 is None else (BWD, (Cy0, Cy1, C0))
+    cin = int(cin_real) if not accum and acc_src is None else 0
+    r = _family(route(op, 5, 1, 0, True, False, a0, a1, o, x0.shape[0], dims, dims, True, cin), "conv-bf16", "conv-bf16-padded")
+    _conv_launch(r, x0, x1, None, bias, y0, y1, accum=accum, stats=stats, res=res, acc_src=acc_src, wp=wp)
+
+
+def _conv2_b16(down, x, w, bias, y, dims_fine, dims_coarse, Cf, Cc, accum=False, stats=None):
+    """The 2^3 stride-2 pair (fp32 or bf16 tensors, by the dtype of x).  down: coarse y = conv(fine x); else fine y (+)= transposed
+    conv(coarse x).  w: the fp32 filter in TF layout, [2,2,2,Cf,Cc] for both."""
+    r = route(FWD, 2, 2, 0 if down else 1, _is16(x), False, Cf if down else Cc, 0, Cc if down else Cf, x.shape[0],
+              dims_fine if down else dims_coarse, dims_coarse if down else dims_fine, w.data_ptr() % 16 == 0)
+    _conv_launch(_family(r, "conv2-direct", "conv2-b16", "conv"), x, None, w, bias, y, accum=accum, stats=stats if down else None)
+
+
+def _wgrad5_b16_call(x0, x1, dy, dw, dims, cin_dw, owner=None):
+    """Filter gradient of the 5^3 stride-1 conv on bf16 tensors (vnet_conv_wgrad_b16, or the grouped launch of a deferring pass)."""
+    r = route(WGRAD, 5, 1, 0, True, False, x0.shape[-1], (x1.shape[-1] if x1 is not None else 0), dy.shape[-1], x0.shape[0], dims, dims,
+              True, int(cin_dw))
+    _wgrad_launch(_family(r, "wgrad-bf16"), x0, x1, dy, dw, owner)
+
+
+def _wgrad2_b16_call(xfine, dycoarse, dw, dims_fine, dims_coarse, owner=None):
+    """Filter gradient of the 2^3 stride-2 conv on bf16 tensors (vnet_conv2_wgrad_b16, or the grouped launch of a deferring pass)."""
+    r = route(WGRAD, 2, 2, 0, True, False, xfine.shape[-1], 0, dycoarse.shape[-1], xfine.shape[0], dims_fine, dims_coarse)
+    _wgrad_launch(_family(r, "wgrad2-b16"), xfine, None, dycoarse, dw, owner)
 
 
 def colsum(x2d_like, C, out=None):
@@ -872,18 +871,17 @@ def _slot_target(slot, dy, shape):
 # gradient is left at exactly 0 in the flat gradient buffer and the 29 column-sum + 29 finalize launches per step are not
 # made.  Stand-alone layers2.convolution (outside the networks) keeps the generic column sum.
 _FUSE = {"zero_bias_grad": False, "bn_stats": True,
-         "bn_stats_fp32_direct": True,
          # round 6: the single-modality input block on the vector pipe straight from the image (csrc/input_block.hip:
          # input_conv_direct_kernel / input_wgrad_direct_kernel); False = rounds 1-5: x-im2col tensor + 5x5x1 fp32-MFMA kernels (A/B runs)
          "input_direct": _os.environ.get("VNET_INPUT_DIRECT", "1") != "0"}
 
 
-def set_epilogue_bn_stats(on, fp32_direct=None):
+def set_epilogue_bn_stats(on, fp32_direct=True):
     """Switch for the batch-norm statistics in the convolution epilogues (on by default; off = separate statistics pass).
-    fp32_direct: also in the epilogue of the non-split fp32 MFMA kernels (on by default; worth 0.07 ms per 128^3 step)."""
+    fp32_direct: the non-split fp32 MFMA kernels write them too -- always (worth 0.07 ms per 128^3 step); False is refused."""
+    if not fp32_direct:
+        raise VnetHipError("set_epilogue_bn_stats: the fp32 MFMA kernels always write the epilogue statistics (fp32_direct=False was retired)")
     _FUSE["bn_stats"] = bool(on)
-    if fp32_direct is not None:
-        _FUSE["bn_stats_fp32_direct"] = bool(fp32_direct)
 
 
 @contextlib.contextmanager
@@ -896,57 +894,48 @@ def zero_bias_gradients(on=True):
         _FUSE["zero_bias_grad"] = prev
 
 
+def _conv_route(op, x0, x1, w, ks, stride, up, dout, res=False):
+    """route() for `op` of the layer with filter w ([k,k,k,I,O]; up: [2,2,2,O,I]) on the forward inputs x0 | x1."""
+    O, I = (w.shape[-2], w.shape[-1]) if up else (w.shape[-1], w.shape[-2])
+    return route(op, ks, stride, up, _is16(x0), _COMPUTE["split3"], x0.shape[-1], (x1.shape[-1] if x1 is not None else 0), O,
+                 x0.shape[0], x0.shape[1:4], dout, w.data_ptr() % 16 == 0, I, res)
+
+
+def _side_stream(dev, wr, db, sb, dw, sw):
+    """The parameter-gradient stream for a node's bias / filter gradient (wr: the filter gradient's route), or None: a gradient
+    autograd has to hand on stays on the main stream, and so does a filter gradient whose launch is being timed (bench.py roofline)."""
+    side = param_grad_stream(dev)
+    if side is None or (db is not None and sb is None) or (dw is not None and sw is None):
+        return None
+    if dw is not None and _timed_tag(wr.tag):
+        return None
+    return side
+
+
 class _ConvFn(torch.autograd.Function):
-    """conv (ks=5,s=1 | ks=2,s=2) or 2^3 transposed conv (up) + bias, two-source input."""
+    """conv (ks=5,s=1 | ks=2,s=2) or 2^3 transposed conv (up) + bias, two-source input; r: the forward's route."""
 
     @staticmethod
-    def forward(ctx, x0, x1, w, b, ks, stride, up, out_spatial, stats=None, res=None):
+    def forward(ctx, x0, x1, w, b, r, stats=None, res=None):
         slot0, slot1 = getattr(x0, "_vnet_slot", None), getattr(x1, "_vnet_slot", None)
         x0 = x0.contiguous()
         x1 = x1.contiguous() if x1 is not None else None
-        B, Di, Hi, Wi, C0 = x0.shape
+        B, C0 = x0.shape[0], x0.shape[-1]
         C1 = x1.shape[-1] if x1 is not None else 0
-        if up:
-            O, I = w.shape[-2], w.shape[-1]
-            dims_out = tuple(int(v) for v in out_spatial)
-            wp = None
-        else:
-            I, O = w.shape[-2], w.shape[-1]
-            dims_out = (_same_out(Di, stride), _same_out(Hi, stride), _same_out(Wi, stride))
-            wp = None
+        O, I = (w.shape[-2], w.shape[-1]) if r.up else (w.shape[-1], w.shape[-2])
         b16 = _is16(x0)            # bf16-storage mode: bf16 tensors in and out (the network input may be zero-padded to 8 channels)
         if I != C0 + C1 and not (b16 and x1 is None and C0 == -(-I // 8) * 8):
             raise VnetHipError("conv: filter expects %d input channels, got %d" % (I, C0 + C1))
         if b16 and (_is16(x1) != (x1 is not None) or (res is not None and not _is16(res))):
             raise VnetHipError("conv: bf16 and float32 tensors mixed")
-        y = torch.empty((B,) + dims_out + (O,), dtype=torch.bfloat16 if b16 else torch.float32, device=x0.device)
-        bf16 = (not up) and ks == 5 and stride == 1 and b16
-        if res is not None:
-            res = res.contiguous()
-        if b16:
-            if x1 is not None and (up or ks != 5):
-                raise VnetHipError("conv: the two-source form exists for the 5^3 convolution only")
-            if up:          # w [2,2,2,O,I]: fine channels O, coarse channels I
-                _conv2_b16(False, x0, w, b, y, dims_out, (Di, Hi, Wi), O, I)
-            elif ks == 2:   # w [2,2,2,I,O]: fine channels I, coarse channels O
-                _conv2_b16(True, x0, w, b, y, (Di, Hi, Wi), dims_out, I, O, stats=stats)
-            else:
-                _conv5_b16_call(x0, x1, packed_weights(w, PACK_FWD_BF16, 125, I, O), b, y, None, dims_out, stats=stats, res=res,
-                                cin_real=(I if x1 is None and I < x0.shape[-1] else 0))
-        elif up and x1 is None:
-            _conv2_b16(False, x0, w, b, y, dims_out, (Di, Hi, Wi), O, I)
-        elif ks == 2 and stride == 2 and x1 is None and res is None:
-            _conv2_b16(True, x0, w, b, y, (Di, Hi, Wi), dims_out, I, O, stats=stats)
-        elif ks == 5 and stride == 1 and not up and _x3_ok(C0, C1, O, 0, B, dims_out):
-            _conv_x3_call(x0, x1, packed_weights(w, PACK_FWD_X3, 125, I, O), b, y, None, dims_out, stats=stats, res=res)
-        else:
-            if wp is None:
-                wp = packed_weights(w, PACK_UP, 8, I, O) if up else packed_weights(w, PACK_FWD, ks ** 3, I, O)
-            _conv_call(ks, stride, 1 if up else 0, x0, x1, wp, b, y, None, (Di, Hi, Wi), dims_out, stats=stats, res=res)
+        if b16 and x1 is not None and (r.up or r.ks != 5):
+            raise VnetHipError("conv: the two-source form exists for the 5^3 convolution only")
+        y = torch.empty((B,) + r.dout + (O,), dtype=torch.bfloat16 if b16 else torch.float32, device=x0.device)
+        _conv_launch(r, x0, x1, w, b, y, stats=stats, res=res.contiguous() if res is not None else None)
         ctx.save_for_backward(x0, x1, w)
         ctx.params = (w, b)
-        ctx.cfg = (ks, stride, up, (Di, Hi, Wi), dims_out, C0, C1, I, O)
-        ctx.bf16 = bf16
+        ctx.cfg = (r.ks, r.stride, r.up, r.din, r.dout, C0, O)
+        ctx.bf16 = b16 and r.ks == 5 and r.stride == 1 and not r.up
         ctx.b16 = b16
         ctx.bias_zero = _FUSE["zero_bias_grad"] and b is not None
         ctx.slots = (slot0, slot1)
@@ -963,9 +952,8 @@ class _ConvFn(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, dy):
         x0, x1, w = ctx.saved_tensors
-        ks, stride, up, din, dout, C0, C1, I, O = ctx.cfg
+        ks, stride, up, din, dout, C0, O = ctx.cfg
         dy = dy.contiguous()
-        B = x0.shape[0]
         dev = x0.device
         wref, bref = ctx.params
         db = dw = None
@@ -976,16 +964,11 @@ class _ConvFn(torch.autograd.Function):
                 bias_zero, sb = True, bref._vnet_sink      # closed form: the flat gradient buffer already holds the exact 0
             else:
                 db, sb = _grad_out(bref)
+        wr = None
         if ctx.needs_input_grad[2]:
             dw, sw = _grad_out(wref)
-        side = param_grad_stream(dev)
-        if side is not None and ((db is not None and sb is None) or (dw is not None and sw is None)):
-            side = None                                  # a gradient autograd has to hand on: stay on the main stream
-        if side is not None and dw is not None and _PROFILE["on"]:
-            wtag = (_wgrad_tag(False, 2, 0, 2, din[2], B, O, I) if up else
-                    _wgrad_tag(ctx.bf16, ks, 0, stride, dout[2], B, C0 + C1, O))
-            if _timed_tag(wtag):
-                side = None                              # a launch that is being timed runs alone (bench.py roofline)
+            wr = _conv_route(WGRAD, x0, x1, w, ks, stride, up, dout)
+        side = _side_stream(dev, wr, db, sb, dw, sw)
         if side is not None:
             main = torch.cuda.current_stream(dev)
             side.wait_stream(main)                       # dy is complete on the main stream
@@ -1014,20 +997,10 @@ class _ConvFn(torch.autograd.Function):
                     colsum16(dy, O, db)
                 else:
                     colsum(dy, O, out=db)
-            if dw is not None and b16:
-                if up:
-                    _wgrad2_b16_call(dy, x0, dw, dout, din, owner=sw)
-                elif stride == 2:
-                    _wgrad2_b16_call(x0, dy, dw, din, dout, owner=sw)
-                else:
-                    _wgrad5_b16_call(x0, x1, dy, dw, din, I, owner=sw)
+            if dw is not None and up:      # the transposed conv's filter gradient: fine dy against coarse x (see route)
+                _wgrad_launch(wr, dy, None, x0, dw, owner=sw)
             elif dw is not None:
-                if up:      # dw[a][o][ci] = sum_i dy[2i+a][o] * x[i][ci]  == filter grad of the 2^3 down conv (fine -> coarse)
-                    _wgrad_call(2, 2, dy, None, x0, dw, dout, din, owner=sw)
-                elif ks == 5 and stride == 1 and _wgrad_x3_ok(C0, C1, O, B, din):
-                    _wgrad_x3_call(x0, x1, dy, dw, din, owner=sw)
-                else:
-                    _wgrad_call(ks, stride, x0, x1, dy, dw, din, dout, owner=sw)
+                _wgrad_launch(wr, x0, x1, dy, dw, owner=sw)
         finally:
             _LAUNCH_ON[0] = None
         dx0 = dx1 = None
@@ -1051,30 +1024,17 @@ class _ConvFn(torch.autograd.Function):
             dx0 = acc if acc is not None else torch.empty_like(x0)
             dx1 = torch.empty_like(x1) if x1 is not None else None
             accum = acc is not None
-            if b16 and up:      # backward-data of the transposed conv = the 2^3 stride-2 conv with the same filter
-                _conv2_b16(True, dy, w, None, dx0, dout, din, O, I, accum=accum)
-            elif b16 and stride == 2:
-                _conv2_b16(False, dy, w, None, dx0, din, dout, I, O, accum=accum)
-            elif b16:
-                _conv5_b16_call(dy, None, packed_weights(w, PACK_BWD_BF16, 125, I, O), None, dx0, dx1, din, accum=accum, acc_src=oop)
-                if oop is not None:
-                    slot0.total = dx0
-            elif up:        # backward-data of the transposed conv = the 2^3 stride-2 conv with the same filter
-                _conv2_b16(True, dy, w, None, dx0, dout, din, O, I, accum=accum)
-            elif stride == 2:   # backward-data of the down conv = the 2^3 transposed conv with the same filter
-                _conv2_b16(False, dy, w, None, dx0, din, dout, I, O, accum=accum)
-            elif ks == 5 and _x3_ok(O, 0, C0, C1, B, din):
-                _conv_x3_call(dy, None, packed_weights(w, PACK_BWD_X3, 125, I, O), None, dx0, dx1, din, accum=accum)
-            else:
-                wp = packed_weights(w, PACK_BWD, ks ** 3, I, O)
-                _conv_call(ks, 1, 0, dy, None, wp, None, dx0, dx1, dout, din, accum=accum)
+            # backward-data of the transposed conv = the 2^3 stride-2 conv with the same filter and vice versa
+            _conv_launch(_conv_route(BWD, x0, x1, w, ks, stride, up, dout), dy, None, w, None, dx0, dx1, accum=accum, acc_src=oop)
+            if oop is not None:
+                slot0.total = dx0
             r0, r1 = (None if accum else dx0), dx1
             if not accum and slot0 is not None and slot0.first is None:
                 slot0.first = dx0                      # first of the two gradients of a forked tensor
             if slot1 is not None and slot1.first is None:
                 slot1.first = dx1
         gb = _grad_ret(db, sb) if (db is not None or bias_zero) else None
-        return r0, r1, _grad_ret(dw, sw), gb, None, None, None, None, None, None
+        return r0, r1, _grad_ret(dw, sw), gb, None, None, None
 
 
 def _meta(*ts):
@@ -1084,10 +1044,11 @@ def _meta(*ts):
 class _InputConvFn(torch.autograd.Function):
     """conv5^3(BN(tile(img))) + b for a 1-channel image without the 16x redundant work (csrc/input_block.hip):
     forward = 5x5x1 conv over the x-im2col of (img, inside-indicator) with BN-folded filters; backward needs only
-    the 2-channel filter gradient G -- dw, and the conv-path parts of the input BN's dgamma/dbeta follow from it."""
+    the 2-channel filter gradient G -- dw, and the conv-path parts of the input BN's dgamma/dbeta follow from it.
+    r: the IN_FWD route."""
 
     @staticmethod
-    def forward(ctx, img, gamma, beta, mean, invstd, w, b, stats=None, res=None):
+    def forward(ctx, img, gamma, beta, mean, invstd, w, b, r, stats=None, res=None):
         L = _lib.lib()
         img = img.contiguous()
         if res is not None:
@@ -1099,22 +1060,20 @@ class _InputConvFn(torch.autograd.Function):
         check(L.vnet_input_conv_fold(_ptr(w), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(wv), C, O, _stream()),
               "vnet_input_conv_fold")
         y = torch.empty((B, D, H, W, O), dtype=torch.float32, device=dev)
-        direct = _input_direct_ok(O, B, D, H, W)
-        if direct:
-            # packed fp32 FMAs straight from the image: no im2col tensor, no filter repack
+        if r.family == "input-direct":
             xv = img
             border = torch.empty(9 * 26 * O, dtype=torch.float32, device=dev)      # wbc [9][25][O] | cbc [9][O]
             check(L.vnet_input_conv_fold_border(_ptr(wv), O, _ptr(border), _ptr(border[9 * 25 * O:]), _stream()), "vnet_input_conv_fold_border")
-            with _Timed("input-direct %d^3x%d 1->%d" % (W, B, O), 2.0 * B * D * H * W * 125 * O, 4.0 * B * D * H * W * (1 + O)):
+            with _Timed(r.tag, r.flops, r.nbytes):
                 check(L.vnet_input_conv_direct_fwd(_ptr(img), _ptr(wv), _ptr(border), _ptr(border[9 * 25 * O:]), _ptr(b), _ptr(res), _ptr(y),
                                                    _ptr(stats), O, B, D, H, W, _stream()), "vnet_input_conv_direct_fwd")
         else:
             xv = torch.empty((B, D, H, W, 16), dtype=torch.float32, device=dev)
             check(L.vnet_tile_im2col_x(_ptr(img), _ptr(xv), B, D, H, W, _stream()), "vnet_tile_im2col_x")
-            wp = torch.empty(L.vnet_packed_weight_floats(PACK_FWD, 25, 16, O), dtype=torch.float32, device=dev)
-            check(L.vnet_pack_weights(PACK_FWD, _ptr(wv), _ptr(wp), 25, 16, O, _stream()), "vnet_pack_weights")
-            _conv_call(5, 1, 0, xv, None, wp, b, y, None, (D, H, W), (D, H, W), kx=1, stats=stats, res=res)
-        ctx.direct = direct
+            wp = torch.empty(L.vnet_packed_weight_floats(*r.pack), dtype=torch.float32, device=dev)
+            check(L.vnet_pack_weights(r.pack[0], _ptr(wv), _ptr(wp), *r.pack[1:], _stream()), "vnet_pack_weights")
+            _conv_launch(r, xv, None, None, b, y, stats=stats, res=res, wp=wp)
+        ctx.wroute = route(IN_WGRAD, 5, 1, 0, False, False, 1, 0, O, B, (D, H, W), (D, H, W))     # (the same reading of the switch)
         ctx.save_for_backward(xv, gamma, beta, mean, invstd, w)
         ctx.params = (w, b)
         ctx.gb = (gamma, beta)
@@ -1136,13 +1095,13 @@ class _InputConvFn(torch.autograd.Function):
             db, sb = _grad_out(bref)
             colsum(dy, O, out=db)
         G = torch.empty((25, 16, O), dtype=torch.float32, device=dev)
-        if ctx.direct:                                   # xv IS the image here
-            nb = L.vnet_input_wgrad_direct_slabs(B, D, H, W) * 25 * 16 * O * 4
-            ws = workspace(nb, dev)
-            with _Timed("input-wgrad-direct %d^3x%d 1->%d" % (W, B, O), 2.0 * B * D * H * W * 125 * O, 4.0 * B * D * H * W * (1 + O)):
-                check(L.vnet_input_wgrad_direct(_ptr(xv), _ptr(dy), _ptr(G), O, B, D, H, W, _ptr(ws), nb, _stream()), "vnet_input_wgrad_direct")
+        wr = ctx.wroute
+        if wr.family == "input-wgrad-direct":          # xv IS the image here
+            ws = workspace(wr.ws, dev)
+            with _Timed(wr.tag, wr.flops, wr.nbytes):
+                check(L.vnet_input_wgrad_direct(_ptr(xv), _ptr(dy), _ptr(G), O, B, D, H, W, _ptr(ws), wr.ws, _stream()), "vnet_input_wgrad_direct")
         else:
-            _wgrad_call(5, 1, xv, None, dy, G, (D, H, W), (D, H, W), kx=1, immediate=True)     # G is folded right below
+            _wgrad_launch(wr, xv, None, dy, G)         # (no owner: G is folded right below)
         dw, sw = _grad_out(wref)
         gpar, bpar = ctx.gb
         gs, bs = getattr(gpar, "_vnet_sink", None), getattr(bpar, "_vnet_sink", None)
@@ -1166,37 +1125,12 @@ class _InputConvFn(torch.autograd.Function):
                     del gpar._vnet_deferred
                     th(0)
             torch.autograd.Variable._execution_engine.queue_callback(flush)
-            return None, None, None, None, None, None, _grad_ret(db, sb), None, None
+            return None, None, None, None, None, None, _grad_ret(db, sb), None, None, None
         dgamma = torch.empty(C, dtype=torch.float32, device=dev)
         dbeta = torch.empty(C, dtype=torch.float32, device=dev)
         check(L.vnet_input_conv_grads(_ptr(G), _ptr(w), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(dw),
                                       _ptr(dgamma), _ptr(dbeta), C, O, 0, _stream()), "vnet_input_conv_grads")
-        return None, dgamma, dbeta, None, None, _grad_ret(dw, sw), _grad_ret(db, sb), None, None
-
-
-def _input_direct_ok(O, B, D, H, W):
-    return _FUSE["input_direct"] and _lib.lib().vnet_input_conv_direct_ok(O, B, D, H, W) == 1
-
-
-def input_conv(img, gamma, beta, mean, invstd, w, b, bn_stats=False, bn_residual=None):
-    """convolution(BN(tf.tile(img)), [5,5,5,C,C]) for a 1-channel `img` (networks.py:254-259 + 316)."""
-    if _meta(img):
-        return torch.empty(img.shape[:-1] + (w.shape[-1],), device="meta")
-    _need_gpu(img, "input_conv")
-    stats = None
-    if bn_stats and _FUSE["bn_stats"] and _FUSE["bn_stats_fp32_direct"] and _SYNC_BN is None:
-        B, D, H, W, _ = img.shape
-        if _input_direct_ok(w.shape[-1], B, D, H, W):
-            rows = _lib.lib().vnet_input_conv_direct_stats_rows(B, D, H, W)
-        else:
-            rows = _lib.lib().vnet_conv_stats_rows(5, 1, 1, 0, 16, w.shape[-1], 0, B, D, H, W)
-        if rows > 0:
-            stats = torch.empty((rows, 2 * w.shape[-1]), dtype=torch.float32, device=img.device)
-    if stats is None:
-        return _InputConvFn.apply(img, gamma, beta, mean, invstd, w, b)
-    y = _InputConvFn.apply(img, gamma, beta, mean, invstd, w, b, stats, bn_residual)
-    y._vnet_stats = _EpilogueStats(stats, stats.shape[0], bn_residual)
-    return y
+        return None, dgamma, dbeta, None, None, _grad_ret(dw, sw), _grad_ret(db, sb), None, None, None
 
 
 class _EpilogueStats(object):
@@ -1208,38 +1142,26 @@ class _EpilogueStats(object):
         self.partial, self.rows, self.residual = partial, rows, residual
 
 
-def _epilogue_stats_buffer(bf16, ks, kx, stride, x0, x1, O, dims_out):
-    if _SYNC_BN is not None:                  # cross-replica statistics need the raw moments of the whole tensor: generic path
-        return None
-    L = _lib.lib()
-    B, C0, C1 = x0.shape[0], x0.shape[-1], (x1.shape[-1] if x1 is not None else 0)
-    if _is16(x0) and not bf16:                # bf16-storage 2^3 stride-2 convolution: one row per workgroup of the direct kernel,
-        if O % 4:                             # or the generic fp32 MFMA kernel's brick rows
-            return None
-        rows = L.vnet_conv2_direct_stats_rows(C0, O, B, *dims_out) if _DIRECT2["on"] else 0
-        if rows <= 0:
-            rows = L.vnet_conv_stats_rows(ks, kx, stride, 0, C0 + C1, O, 0, B, *dims_out)
-    elif bf16:
-        # (the kernels that stage bf16 sources have their own brick shapes: one partial row per brick)
-        rows = L.vnet_conv_b16_stats_rows(C0, C1, O, 0, B, *dims_out)     # (the deep-level kernel has its own bricks: csrc/conv_deep.h)
-    else:
-        # fp32 MFMA kernels: measured (profiles/r02_epilogue_stats.txt) the STATS instantiations lose in their main loop most of
-        # what the statistics pass costs (+1..3 % per launch, residual re-read on the input conv): the fused form is worth
-        # 0.07 ms of a 25.7 ms step; `_FUSE["bn_stats_fp32_direct"] = False` keeps it to the split-K launches (statistics from the reduce kernel)
-        rows = 0
-        # (NOT conditional on bn_stats_fp32_direct -- _ConvFn.forward takes the f32x3 kernel whenever _x3_ok, and the buffer
-        #  must have that kernel's row count whatever the fp32-MFMA switch says)
-        if ks == 5 and stride == 1 and kx in (0, 5) and _x3_ok(C0, C1, O, 0, B, dims_out):
-            rows = L.vnet_conv_x3_stats_rows(C0 + C1, O, B, *dims_out)        # f32x3 kernel: one row per 2x8x16 brick (or per reduce block)
-        if ks == 2 and stride == 2 and x1 is None and _DIRECT2["on"]:
-            rows = L.vnet_conv2_direct_stats_rows(C0, O, B, *dims_out)        # the LDS-free direct kernel (levels 1-2): one row per workgroup
-        if rows <= 0:
-            if not _FUSE["bn_stats_fp32_direct"] and not L.vnet_conv_stats_from_reduce(ks, kx, stride, C0 + C1, O, B, *dims_out):
-                return None
-            rows = L.vnet_conv_stats_rows(ks, kx, stride, 0, C0 + C1, O, 0, B, *dims_out)
-    if rows <= 0:
-        return None
-    return torch.empty((rows, 2 * O), dtype=torch.float32, device=x0.device)
+def _with_epilogue_stats(fn, args, r, O, bn_stats, bn_residual, device):
+    """fn.apply(*args) for the forward route r; with bn_stats (and the fused statistics on) its epilogue also writes the partial sums
+    of the batch-norm behind it into a buffer of r.stats_rows rows (cross-replica statistics need the raw moments of the whole
+    tensor: the generic path)."""
+    if not (bn_stats and _FUSE["bn_stats"] and _SYNC_BN is None and r.stats_rows > 0):
+        return fn.apply(*args)
+    stats = torch.empty((r.stats_rows, 2 * O), dtype=torch.float32, device=device)
+    y = fn.apply(*args, stats, bn_residual)
+    y._vnet_stats = _EpilogueStats(stats, r.stats_rows, bn_residual)
+    return y
+
+
+def input_conv(img, gamma, beta, mean, invstd, w, b, bn_stats=False, bn_residual=None):
+    """convolution(BN(tf.tile(img)), [5,5,5,C,C]) for a 1-channel `img` (networks.py:254-259 + 316)."""
+    if _meta(img):
+        return torch.empty(img.shape[:-1] + (w.shape[-1],), device="meta")
+    _need_gpu(img, "input_conv")
+    B, D, H, W, _ = img.shape
+    r = route(IN_FWD, 5, 1, 0, False, False, 1, 0, w.shape[-1], B, (D, H, W), (D, H, W))
+    return _with_epilogue_stats(_InputConvFn, (img, gamma, beta, mean, invstd, w, b, r), r, w.shape[-1], bn_stats, bn_residual, img.device)
 
 
 def conv(x0, w, b, ks, stride=1, x1=None, bn_stats=False, bn_residual=None):
@@ -1252,16 +1174,10 @@ def conv(x0, w, b, ks, stride=1, x1=None, bn_stats=False, bn_residual=None):
         B, D, H, W, _ = x0.shape
         return torch.empty((B, _same_out(D, stride), _same_out(H, stride), _same_out(W, stride), w.shape[-1]), device="meta")
     _need_gpu(x0, "conv", allow16=True)
-    stats = None
-    if bn_stats and _FUSE["bn_stats"]:
-        dims_out = tuple(_same_out(int(v), stride) for v in x0.shape[1:4])
-        bf16 = ks == 5 and stride == 1 and _is16(x0)
-        stats = _epilogue_stats_buffer(bf16, ks, 0, stride, x0, x1, w.shape[-1], dims_out)
-    if stats is None:
-        return _ConvFn.apply(x0, x1, w, b, ks, stride, False, None)
-    y = _ConvFn.apply(x0, x1, w, b, ks, stride, False, None, stats, bn_residual)
-    y._vnet_stats = _EpilogueStats(stats, stats.shape[0], bn_residual)
-    return y
+    fused = bn_stats and _FUSE["bn_stats"] and _SYNC_BN is None
+    r = _conv_route(FWD, x0, x1, w, ks, stride, False, tuple(_same_out(int(v), stride) for v in x0.shape[1:4]),
+                    res=fused and bn_residual is not None)
+    return _with_epilogue_stats(_ConvFn, (x0, x1, w, b, r), r, w.shape[-1], bn_stats, bn_residual, x0.device)
 
 
 def conv_transpose2(x, w, b, out_spatial):
@@ -1271,7 +1187,7 @@ def conv_transpose2(x, w, b, out_spatial):
     if _meta(x):
         return torch.empty((x.shape[0],) + tuple(out_spatial) + (w.shape[-2],), device="meta")
     _need_gpu(x, "conv_transpose2", allow16=True)
-    return _ConvFn.apply(x, None, w, b, 2, 2, True, tuple(out_spatial))
+    return _ConvFn.apply(x, None, w, b, _conv_route(FWD, x, None, w, 2, 2, True, out_spatial))
 
 
 # ---- batch-norm (+residual, +tile, +activation) -------------------------------------------------------
