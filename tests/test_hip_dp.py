@@ -4,6 +4,7 @@ device, but everything around it is the production code: gradient sinks -> bucke
 all-reduce launched from backward on the side stream -> 1/world scaling in the fused Adam kernel.
 Checks SURVEY 8(e): all-reduced gradient == sum of the per-rank single-process gradients (per-replica BN),
 replicas stay bit-identical, and the update equals single-process Adam on the mean gradient."""
+import contextlib
 import os
 import socket
 
@@ -45,7 +46,8 @@ def _build(dev, seed):
     np.random.seed(seed)
     compute = os.environ.get("VNET_TEST_COMPUTE", "fp32")      # "bf16": bf16 tensors end to end (needs 8 * 2^k channels)
     ops.set_compute_dtype(compute)
-    net = networks.VNet(NET["K"], 0.0, 8 if compute == "bf16" else NET["C0"], NET["levels"], NET["ncv"], NET["nb"], True, "prelu", device=dev)
+    C0 = {"bf16": 8, "fp32_split3": 16}.get(compute, NET["C0"])     # (fp32_split3: whole 16-channel blocks, the f32x3 kernels' unit)
+    net = networks.VNet(NET["K"], 0.0, C0, NET["levels"], NET["ncv"], NET["nb"], True, "prelu", device=dev)
     net.build((1, NET["P"], NET["P"], NET["P"], 1))
     return net
 
@@ -115,6 +117,11 @@ def _worker(rank, world, port, out, backend="gloo"):
     dev = _rank_env(rank, world, port, backend)
     import torch.distributed as dist
     from vnet_tensorflow_amd import ops, optim, parallel
+    from tests.util import split3, x3_profile_check
+    x3 = os.environ.get("VNET_TEST_COMPUTE") == "fp32_split3"
+    keep = contextlib.ExitStack()
+    if x3:
+        keep.enter_context(split3(force=True))   # every 5^3 layer on the f32x3 kernels: a spawned worker does not inherit ops._X3
     parallel.init_from_env()
     assert dist.get_backend() == backend and dist.get_world_size() == world
     net = _build(dev, seed=100 + rank)                 # replicas start different ...
@@ -131,24 +138,30 @@ def _worker(rank, world, port, out, backend="gloo"):
     for step in range(2):                              # step 0 calibrates the event counts, step 1 overlaps
         flat.zero_grad()
         sync.begin_step()
+        if x3 and step == 0:
+            ops.profile_start()
         loss, _, _, _ = ops.softmax_loss(net.GetNetwork(x), lab, "sorensen")
         loss.backward()
         if step == 1:
             assert sum(sync._launched) >= len(sync.buckets) - 1      # buckets went out DURING backward
         sync.finish()
         ops.join_param_grad_stream()
+        if x3 and step == 0:
+            x3_profile_check(ops.profile_stop(), forced=True)      # the gradients the hooks exchanged came from the f32x3 kernels
         torch.cuda.synchronize()
         gsum = flat.grad.clone()
         opt.apply(1e-2)
     torch.cuda.synchronize()
     torch.save({"gsum": gsum.cpu(), "data": flat.data.cpu(), "loss": float(loss.detach())}, os.path.join(out, "r%d.pt" % rank))
     dist.destroy_process_group()
+    keep.close()
 
 
-@pytest.mark.parametrize("compute", ["fp32", "bf16", "bf16+bf16comm"])
+@pytest.mark.parametrize("compute", ["fp32", "bf16", "bf16+bf16comm", "fp32_split3"])
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_two_ranks(tmp_path, dev, backend, compute, monkeypatch):
     from vnet_tensorflow_amd import ops, optim
+    from tests.util import split3
     comm16 = compute.endswith("bf16comm")                  # round 6: GradCommDtype "bf16" -- bf16 buckets on the links, fp32 accumulation on receipt
     compute = compute.split("+")[0]
     monkeypatch.setenv("VNET_TEST_COMPUTE", compute)       # (bf16: bf16 storage -- the per-GPU arithmetic of BASELINE config C5)
@@ -156,12 +169,14 @@ def test_two_ranks(tmp_path, dev, backend, compute, monkeypatch):
         monkeypatch.setenv("VNET_TEST_PG", "0")            # as the product step: no side stream, gradients accumulate in the epilogues
     if comm16:
         monkeypatch.setenv("VNET_TEST_COMM", "bf16")
+    # (bf16 buckets: the single-process reference applies the SAME exchange arithmetic to its per-rank gradients -- RNE to bf16 per
+    #  rank, fp32 sum in rank order, one rounding -- so the tolerances stay those of the bf16 mode.  Against the fp32 sum the second
+    #  step would differ by ~1e-2: Adam's first step moves every parameter by ~lr x sign(g), and the rounding flips signs of the
+    #  near-zero gradients.)
+    tol = (1e-5, 1e-4, 1e-5) if compute in ("fp32", "fp32_split3") else (2e-4, 2e-3, 2e-4)
     try:
-        # (bf16 buckets: the single-process reference applies the SAME exchange arithmetic to its per-rank gradients -- RNE to bf16 per
-        #  rank, fp32 sum in rank order, one rounding -- so the tolerances stay those of the bf16 mode.  Against the fp32 sum the second
-        #  step would differ by ~1e-2: Adam's first step moves every parameter by ~lr x sign(g), and the rounding flips signs of the
-        #  near-zero gradients.)
-        _two_ranks(tmp_path, dev, backend, tol=(1e-5, 1e-4, 1e-5) if compute == "fp32" else (2e-4, 2e-3, 2e-4), comm16=comm16)
+        with (split3(force=True) if compute == "fp32_split3" else contextlib.nullcontext()):     # (the single-process reference too)
+            _two_ranks(tmp_path, dev, backend, tol=tol, comm16=comm16)
     finally:
         ops.set_compute_dtype("fp32")
 

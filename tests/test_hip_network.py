@@ -168,29 +168,44 @@ def test_ragged_architectures_live_oracle(dev, variant, cin, K, C0, levels, ncv,
     assert np.sqrt(num / den) < 1e-3, np.sqrt(num / den)
 
 
-def test_training_steps_match_oracle_adam(dev):
-    """Three optimiser steps (TF-form Adam + exponential LR decay, model.py:641-666) track the oracle."""
+@pytest.mark.parametrize("compute,C0", [("fp32", 4), ("fp32", 16), ("fp32_split3", 16)],
+                         ids=["fp32-c4", "fp32-c16", "fp32_split3-c16-forced"])
+def test_training_steps_match_oracle_adam(dev, compute, C0):
+    """Three optimiser steps (TF-form Adam + exponential LR decay, model.py:641-666) track the oracle.  fp32_split3: every 5^3
+    layer forced onto the f32x3 kernels (width 16: whole 16-channel blocks), with the repack of their PACK_*_X3 images after each
+    step; the native fp32 run at the same width is the control, under the same bounds."""
+    import contextlib
     from vnet_tensorflow_amd import ops, optim
+    from tests.util import split3, x3_profile_check
     ps = O.ParamStore(rng=np.random.default_rng(9), perturb=0.1)
-    ref_net = O.VNetOracle(2, 0.0, 4, 2, (1, 2), 2, "prelu", "networks", ps)
+    ref_net = O.VNetOracle(2, 0.0, C0, 2, (1, 2), 2, "prelu", "networks", ps)
     x, lab = O.synthetic_batch(2, 16, 1, 2, seed=4000)
     ref_net.GetNetwork(x.astype(np.float64))
-    net = _build(dev, "networks", 2, 4, 2, (1, 2), 2, {k: v.v for k, v in ps.vars.items()}, x.shape)
-    flat = optim.FlatParams(net.named_parameters())
-    opt = optim.AdamOptimizer(flat)
-    adam = O.TFAdam()
-    tx, tl = g(x, dev), g(lab, dev, torch.int32)
-    for step in range(3):
-        lr = optim.exponential_decay(1e-3, step, 100, 0.99)
-        ref = O.run_step(x.astype(np.float64), lab, ref_net, "sorensen")
-        params = adam.step({k: v.v for k, v in ps.vars.items()}, ref["grads"], lr)
-        for k, v in params.items():
-            ps.vars[k].v = v
-        flat.zero_grad()
-        loss, _, _, _ = ops.softmax_loss(net.GetNetwork(tx), tl, "sorensen")
-        loss.backward()
-        opt.apply(lr)
-        assert abs(float(loss) - ref["loss"]) < 2e-5, (step, float(loss), ref["loss"])
+    with (split3(force=True) if compute == "fp32_split3" else contextlib.nullcontext()):
+        net = _build(dev, "networks", 2, C0, 2, (1, 2), 2, {k: v.v for k, v in ps.vars.items()}, x.shape)
+        flat = optim.FlatParams(net.named_parameters())
+        opt = optim.AdamOptimizer(flat)
+        adam = O.TFAdam()
+        tx, tl = g(x, dev), g(lab, dev, torch.int32)
+        for step in range(3):
+            lr = optim.exponential_decay(1e-3, step, 100, 0.99)
+            ref = O.run_step(x.astype(np.float64), lab, ref_net, "sorensen")
+            params = adam.step({k: v.v for k, v in ps.vars.items()}, ref["grads"], lr)
+            for k, v in params.items():
+                ps.vars[k].v = v
+            flat.zero_grad()
+            ops.profile_start()
+            try:
+                loss, _, _, _ = ops.softmax_loss(net.GetNetwork(tx), tl, "sorensen")
+                loss.backward()
+                opt.apply(lr)
+            finally:
+                recs = ops.profile_stop()
+            if compute == "fp32_split3":
+                x3_profile_check(recs, forced=True)
+            else:
+                assert not any(r[0].startswith(("conv-x3", "wgrad-x3")) for r in recs)
+            assert abs(float(loss) - ref["loss"]) < 2e-5, (step, float(loss), ref["loss"])
     for n, p in net.named_parameters():
         check_close("after 3 steps " + n, p, ps.vars[n].v, 2e-3, atol=2e-4)
 

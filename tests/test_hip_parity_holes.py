@@ -1,5 +1,6 @@
 """-m gpu: parity items VERDICT r1 listed as open (#8): dropout against the oracle with the kernel's own mask, the native
 C++ inference driver against the ORACLE (not against the Python HIP path), tf.metrics.auc, streaming metrics."""
+import contextlib
 import os
 import subprocess
 
@@ -181,33 +182,46 @@ def test_conv_bias_gradient_closed_form(dev, variant):
     assert nb >= 8
 
 
-@pytest.mark.parametrize("compute", ["fp32"])
+@pytest.mark.parametrize("compute", ["fp32", "fp32_split3"])
 def test_gradient_accumulation_in_the_producing_kernel(dev, compute):
     """Tensors with two consumers (skip connection, residual block input): the second gradient is added by the backward-data
     kernel that produces it (y += ..., ops.fork) instead of an autodiff add kernel.  Same two fp32 numbers are added either
-    way, so every gradient is bit-identical to the unfused graph; and the fused pass really runs no add kernel."""
+    way, so every gradient is bit-identical to the unfused graph; and the fused pass really runs no add kernel.
+    fp32_split3: width 16 with every 5^3 layer forced onto the f32x3 kernels -- vnet_conv_fwd_x3 in accumulate mode (acc = y0),
+    at the deep levels through the K-split reduce; the fused backward must show conv-x3 launches."""
     from vnet_tensorflow_amd import networks, ops, optim
+    from tests.util import split3, x3_profile_check
     x, lab = O.synthetic_batch(1, 32, 2, 3, seed=5)
     grads = {}
-    ops.set_compute_dtype(compute)
-    try:
-        for fuse in (True, False):
-            np.random.seed(11)
-            net = networks.VNet(3, 0.0, 8, 3, (1, 2, 3), 2, True, "prelu", device=dev)
-            net.fuse_grad_accumulation = fuse
-            net.build(x.shape)
-            flat = optim.FlatParams(net.named_parameters())
-            flat.zero_grad()
-            from torch.profiler import profile, ProfilerActivity
-            with profile(activities=[ProfilerActivity.CPU]) as prof:
-                loss, _, _, _ = ops.softmax_loss(net.GetNetwork(g(x, dev)), g(lab, dev, torch.int32), "sorensen")
-                loss.backward()
-            torch.cuda.synchronize()
-            adds = sum(1 for e in prof.events() if e.name == "aten::add" and e.input_shapes != [])
-            big_adds = [e for e in prof.events() if e.name in ("aten::add", "aten::add_")]
-            grads[fuse] = ({n: p.grad.detach().cpu().numpy().copy() for n, p in net.named_parameters()}, len(big_adds))
-    finally:
-        ops.set_compute_dtype("fp32")
+    x3 = compute == "fp32_split3"
+    width = 16 if x3 else 8                    # (8 channels cannot route to the f32x3 kernels: whole 16-channel blocks only)
+    with (split3(force=True) if x3 else contextlib.nullcontext()):
+        ops.set_compute_dtype(compute)
+        try:
+            for fuse in (True, False):
+                np.random.seed(11)
+                net = networks.VNet(3, 0.0, width, 3, (1, 2, 3), 2, True, "prelu", device=dev)
+                net.fuse_grad_accumulation = fuse
+                net.build(x.shape)
+                flat = optim.FlatParams(net.named_parameters())
+                flat.zero_grad()
+                from torch.profiler import profile, ProfilerActivity
+                with profile(activities=[ProfilerActivity.CPU]) as prof:
+                    loss, _, _, _ = ops.softmax_loss(net.GetNetwork(g(x, dev)), g(lab, dev, torch.int32), "sorensen")
+                    if fuse and x3:
+                        ops.profile_start()
+                    try:
+                        loss.backward()
+                    finally:
+                        recs = ops.profile_stop() if fuse and x3 else None
+                torch.cuda.synchronize()
+                if recs is not None:
+                    x3_profile_check(recs, forced=True)        # (the backward pass alone: its backward-data launches are conv-x3)
+                adds = sum(1 for e in prof.events() if e.name == "aten::add" and e.input_shapes != [])
+                big_adds = [e for e in prof.events() if e.name in ("aten::add", "aten::add_")]
+                grads[fuse] = ({n: p.grad.detach().cpu().numpy().copy() for n, p in net.named_parameters()}, len(big_adds))
+        finally:
+            ops.set_compute_dtype("fp32")
     for n in grads[True][0]:
         assert np.array_equal(grads[True][0][n], grads[False][0][n]), n
     # 3 levels: 3 skip forks + residual forks at levels 2, 3 and the bottom = 6 full-tensor adds saved
@@ -287,41 +301,76 @@ def test_batched_filter_repack_equals_single_pack(dev, taps, I, O):
         ops.clear_pack_registry()
 
 
-@pytest.mark.parametrize("compute,cin", [("fp32", 1), ("fp32", 2), ("bf16", 4)])
-def test_deferred_batched_filter_gradient_reduce(dev, compute, cin):
+@pytest.mark.parametrize("compute,cin", [("fp32", 1), ("fp32", 2), ("bf16", 4), ("fp32_split3", 1), ("fp32_split3", 2)])
+def test_deferred_batched_filter_gradient_reduce(dev, compute, cin, monkeypatch):
     """ops.deferred_wgrad_reduce: the filter-gradient launches leave their partial slabs in per-layer buffers and ONE launch
     reduces all of them at the end of the backward pass (vnet_wgrad_defer / vnet_wgrad_flush).  Same summation order as the
     per-layer reduce: every gradient bit-identical; the queue really fills and really drains; the fused input block's G
-    (consumed inside backward) is still reduced on the spot."""
+    (consumed inside backward) is still reduced on the spot.  fp32_split3 (every 5^3 layer forced onto the f32x3 kernels): the
+    queue length is derived from the routes -- each wgrad-x3 launch whose route asks for more than one slab (ws = slabs x 125 x
+    Cin x Cout x 4 bytes) queues exactly one reduce, a one-slab launch none -- and the queue holds nothing but what the filter-
+    gradient launches put there."""
     from vnet_tensorflow_amd import networks, ops, optim
     from vnet_tensorflow_amd._lib import lib
+    from tests.util import split3, x3_profile_check
     L = lib()
+    x3 = compute == "fp32_split3"
     x, lab = O.synthetic_batch(1, 32, cin, 3, seed=5)
-    grads, queued = {}, {}
-    ops.set_compute_dtype(compute)
+    grads, queued, launched = {}, {}, {}
+    log = []
+    wgrad_launch = ops._wgrad_launch
+
+    def spy(r, *a, **k):                           # queue length around each filter-gradient launch of the pass
+        st = ops._stream()
+        n0 = L.vnet_wgrad_pending(st)
+        wgrad_launch(r, *a, **k)
+        log.append((r, L.vnet_wgrad_pending(st) - n0))
+    monkeypatch.setattr(ops, "_wgrad_launch", spy)
     # (round 4: a deferring pass in bf16 storage ALSO launches its deep-level filter gradients as one group, which splits the layers
     #  differently -- another summation order; that path has its own tests in tests/test_hip_wgrad_group.py.  Here: the reduce.)
-    ops.set_wgrad_group(False)
-    try:
-        for defer in (True, False):
-            np.random.seed(11)
-            net = networks.VNet(3, 0.0, 16, 3, (1, 2, 3), 2, True, "prelu", device=dev)
-            net.build(x.shape)
-            flat = optim.FlatParams(net.named_parameters())
-            for rep in range(2):                   # second pass: the per-layer slab buffers are reused
-                flat.zero_grad()
-                loss, _, _, _ = ops.softmax_loss(net.GetNetwork(g(x, dev)), g(lab, dev, torch.int32), "sorensen")
-                with ops.deferred_wgrad_reduce(defer):
-                    loss.backward()
-                    ops.join_param_grad_stream()
-                    queued[defer] = L.vnet_wgrad_pending(ops._stream())
-                assert L.vnet_wgrad_pending(ops._stream()) == 0
-            torch.cuda.synchronize()
-            grads[defer] = {n: p.grad.detach().cpu().numpy().copy() for n, p in net.named_parameters()}
-    finally:
-        ops.set_compute_dtype("fp32")
-        ops.set_wgrad_group(True)
+    with (split3(force=True) if x3 else contextlib.nullcontext()):
+        ops.set_compute_dtype(compute)
+        ops.set_wgrad_group(False)
+        try:
+            for defer in (True, False):
+                np.random.seed(11)
+                net = networks.VNet(3, 0.0, 16, 3, (1, 2, 3), 2, True, "prelu", device=dev)
+                net.build(x.shape)
+                flat = optim.FlatParams(net.named_parameters())
+                for rep in range(2):                   # second pass: the per-layer slab buffers are reused
+                    flat.zero_grad()
+                    del log[:]
+                    if x3 and rep == 0:
+                        ops.profile_start()
+                    try:
+                        loss, _, _, _ = ops.softmax_loss(net.GetNetwork(g(x, dev)), g(lab, dev, torch.int32), "sorensen")
+                        with ops.deferred_wgrad_reduce(defer):
+                            loss.backward()
+                            ops.join_param_grad_stream()
+                            queued[defer] = L.vnet_wgrad_pending(ops._stream())
+                    finally:
+                        recs = ops.profile_stop() if x3 and rep == 0 else None
+                    if recs is not None:
+                        x3_profile_check(recs, forced=True)
+                    assert L.vnet_wgrad_pending(ops._stream()) == 0
+                    launched[defer] = list(log)
+                torch.cuda.synchronize()
+                grads[defer] = {n: p.grad.detach().cpu().numpy().copy() for n, p in net.named_parameters()}
+        finally:
+            ops.set_compute_dtype("fp32")
+            ops.set_wgrad_group(True)
     assert queued[False] == 0 and queued[True] >= 10, queued
+    if x3:
+        x3l = [(r, d) for r, d in launched[True] if r.family == "wgrad-x3"]
+        assert x3l, [r.family for r, _ in launched[True]]
+        for r, d in x3l:
+            cout = int(r.tag.rsplit("->", 1)[1])
+            slabs, rem = divmod(r.ws, 125 * r.cin * cout * 4)
+            assert rem == 0 and slabs >= 1, (r.tag, r.ws)
+            assert d == (1 if slabs >= 2 else 0), (r.tag, slabs, d)       # partial slabs: the reduce waits in the queue
+        assert sum(d for _, d in x3l) >= 1, [(r.tag, r.ws) for r, _ in x3l]
+        assert queued[True] == sum(d for _, d in launched[True]), (queued, [(r.tag, d) for r, d in launched[True]])
+        assert all(d == 0 for _, d in launched[False])
     for n in grads[True]:
         assert np.array_equal(grads[True][n], grads[False][n]), n
     assert all(np.isfinite(v).all() for v in grads[True].values())

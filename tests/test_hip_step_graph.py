@@ -2,6 +2,7 @@
 sess.run per step).  The graph holds exactly the launches the eager step makes -- forward, loss, backward on two
 streams, fused optimiser, batched filter repack -- with the per-step scalars (learning rate, Adam's lr_t, dropout
 stream position) read from the device step state, so replay must be BIT-identical to the eager step."""
+import contextlib
 import os
 import pathlib
 import socket
@@ -15,13 +16,13 @@ import torch.multiprocessing as mp
 pytestmark = pytest.mark.gpu
 
 
-def _cfg(P=16, dropout=0.0, opt="Adam", compute="fp32", cin=1, K=2, loss="sorensen"):
+def _cfg(P=16, dropout=0.0, opt="Adam", compute="fp32", cin=1, K=2, loss="sorensen", nch=8):
     return {"TrainingSetting": {
         "Data": {"TrainingDataDirectory": "synthetic", "TestingDataDirectory": "synthetic",
                  "ImageFilenames": ["image%d.npy" % i for i in range(cin)], "LabelFilename": "label.npy",
                  "Synthetic": {"Cases": 4}},
         "SegmentationClasses": list(range(K)), "BatchSize": 2, "PatchShape": [P] * 3, "ComputeDtype": compute,
-        "Networks": {"Name": "VNet", "Dropout": dropout, "NumChannel": 8, "NumLevels": 3, "NumConvolutions": [1, 2, 2],
+        "Networks": {"Name": "VNet", "Dropout": dropout, "NumChannel": nch, "NumLevels": 3, "NumConvolutions": [1, 2, 2],
                      "BottomConvolutions": 2},
         "Loss": {"Name": loss, "Weights": [0.3, 0.7, 1.0, 0.5, 0.2][:K], "Alpha": 0.5},
         "Optimizer": {"Name": opt, "InitialLearningRate": 1e-2, "Momentum": 0.9, "Decay": {"Factor": 0.9, "Steps": 3}}}}
@@ -57,17 +58,55 @@ def _run(dev, graph, steps, monkeypatch, **kw):
     return losses, m.flat.data.clone(), state, {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in m.optimizer.state_dict().items()}
 
 
+def _x3_dispatch(dev, monkeypatch, force, **kw):
+    """One EAGER training step of the configuration under ops.profile_start(): which 5^3 kernels the step really launches (a
+    captured graph records none, so this runs apart from the steps compared bit for bit)."""
+    from vnet_tensorflow_amd import ops
+    from vnet_tensorflow_amd.model import image2label
+    from oracle.vnet_oracle import synthetic_batch
+    from tests.util import x3_profile_check
+    monkeypatch.setenv("VNET_STEP_GRAPH", "0")
+    cfg = _cfg(**kw)
+    T = cfg["TrainingSetting"]
+    cin, K, P = len(T["Data"]["ImageFilenames"]), len(T["SegmentationClasses"]), T["PatchShape"][0]
+    np.random.seed(7)
+    m = image2label(None, cfg, device=dev, verbose=False)
+    m.read_config()
+    m.build_model_graph()
+    m._setup_training()
+    x, l = synthetic_batch(2, P, cin, K, seed=40)
+    ops.profile_start()
+    try:
+        m.train_step(torch.from_numpy(x).to(dev), torch.from_numpy(l).to(dev))
+    finally:
+        recs = ops.profile_stop()
+    assert m._graph_mode() == "off"
+    return x3_profile_check(recs, force)
+
+
 @pytest.mark.parametrize("kw", [
-    dict(),                                                       # Adam, no dropout (the bench configuration)
+    dict(),                                                       # Adam, no dropout, native fp32 kernels
     dict(dropout=0.05),                                           # dropout masks from the device step state
     dict(opt="NesterovMomentum", loss="mixed_weighted_jaccard", cin=2, K=3),
     dict(opt="SGD", compute="bf16", cin=4, K=5),                  # BASELINE config C5 arithmetic
-], ids=["adam", "dropout", "nesterov-mixed", "sgd-bf16"])
+    # fp32_split3 (the bench's headline arithmetic) as the product dispatches it: level 1, 32^3 x 2 16 -> 16, takes the f32x3 kernels
+    dict(P=32, nch=16, compute="fp32_split3"),
+    # forced: EVERY 5^3 layer on the f32x3 kernels -- the 8^3 narrow brick, the 4^3 level, K split with partial slabs
+    dict(P=16, nch=16, compute="fp32_split3", force_x3=True),
+], ids=["adam", "dropout", "nesterov-mixed", "sgd-bf16", "adam-x3", "adam-x3-forced"])
 def test_graph_replay_is_bit_identical_to_eager(dev, monkeypatch, kw):
     """6 steps: 2 eager warm-up steps + capture + 4 replays against 6 eager steps -- same losses, parameters, moving
-    statistics and optimiser slots, bit for bit (LR decays every step, so a frozen scalar would show)."""
-    a = _run(dev, True, 6, monkeypatch, **kw)
-    b = _run(dev, False, 6, monkeypatch, **kw)
+    statistics and optimiser slots, bit for bit (LR decays every step, so a frozen scalar would show).  fp32_split3: the
+    captured step holds the f32x3 launches, their K-split workspaces and the PACK_*_X3 images of the batched repack; a
+    separate eager step proves the f32x3 kernels ran."""
+    from tests.util import split3
+    kw = dict(kw)
+    force = kw.pop("force_x3", False)
+    with (split3(force) if kw.get("compute") == "fp32_split3" else contextlib.nullcontext()):
+        if kw.get("compute") == "fp32_split3":
+            _x3_dispatch(dev, monkeypatch, force, **kw)
+        a = _run(dev, True, 6, monkeypatch, **kw)
+        b = _run(dev, False, 6, monkeypatch, **kw)
     assert a[0] == b[0], (a[0], b[0])
     assert torch.equal(a[1], b[1])
     for k in a[2]:

@@ -66,20 +66,25 @@ def test_train_checkpoint_restore_evaluate(tmp_path, dev):
     assert np.allclose(p0 + p1, 1.0, atol=1e-5) and ((p1 > p0) == (lab == 1)).mean() > 0.999
 
 
-@pytest.mark.parametrize("compute,cin,K", [("fp32", 1, 2), ("bf16", 4, 5)])
+@pytest.mark.parametrize("compute,cin,K", [("fp32", 1, 2), ("bf16", 4, 5), ("fp32_split3", 1, 2)])
 def test_loss_decreases_on_fixed_batch(dev, compute, cin, K):
     """Sanity of the whole fwd/bwd/Adam loop: 12 steps on one synthetic batch reduce the Dice loss -- in the
-    reference's fp32 arithmetic and in the bf16-compute mode of BASELINE config C5 (4 modalities, 5 classes; this also
-    runs the batched bf16 filter repack after every optimiser step)."""
+    reference's fp32 arithmetic, in the bf16-compute mode of BASELINE config C5 (4 modalities, 5 classes; this also
+    runs the batched bf16 filter repack after every optimiser step) and in fp32_split3 with every 5^3 layer forced onto the
+    f32x3 kernels (the first, eager, step proves they ran)."""
+    import contextlib
     from vnet_tensorflow_amd import ops
     from vnet_tensorflow_amd.model import image2label
     from oracle.vnet_oracle import synthetic_batch
+    from tests.util import split3, x3_profile_check
     import pathlib
     np.random.seed(1)
     cfg = _cfg(pathlib.Path("/tmp"), ComputeDtype=compute, SegmentationClasses=list(range(K)))
     cfg["TrainingSetting"]["Data"]["ImageFilenames"] = ["image%d.npy" % i for i in range(cin)]
     if compute == "bf16":
         cfg["TrainingSetting"]["Networks"]["NumChannel"] = 8          # bf16 storage: 16-byte channel units
+    if compute == "fp32_split3":
+        cfg["TrainingSetting"]["Networks"]["NumChannel"] = 16         # whole 16-channel blocks: the f32x3 kernels' unit
     m = image2label(None, cfg, device=dev, verbose=False)
     try:
         m.read_config()
@@ -88,7 +93,15 @@ def test_loss_decreases_on_fixed_batch(dev, compute, cin, K):
         m._setup_training()
         x, lab = synthetic_batch(2, 16, cin, K, seed=11)
         xt, lt = torch.from_numpy(x).to(dev), torch.from_numpy(lab).to(dev)
-        losses = [float(m.train_step(xt, lt, dropout=0.0)) for _ in range(12)]
+        with (split3(force=True) if compute == "fp32_split3" else contextlib.nullcontext()):
+            ops.profile_start()
+            try:
+                losses = [float(m.train_step(xt, lt, dropout=0.0))]
+            finally:
+                recs = ops.profile_stop()
+            if compute == "fp32_split3":
+                x3_profile_check(recs, forced=True)
+            losses += [float(m.train_step(xt, lt, dropout=0.0)) for _ in range(11)]
     finally:
         ops.set_compute_dtype("fp32")
     assert all(np.isfinite(losses)) and losses[-1] < losses[0] - 0.05, losses
