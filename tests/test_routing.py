@@ -2,7 +2,11 @@
 the record -- family, launch tag, workspace bytes, epilogue statistics rows, flops and bytes -- matches a table recorded from the
 launches of one eager training step per network and mode (tags and workspace queries in launch order, and the `_vnet_stats`
 rows of every convolution output, before routing moved into one function).  And the side-stream guard of a filter gradient
-reads the same tag the launch carries."""
+reads the same tag the launch carries.
+
+Batch-norm routing (ops.bn_route) likewise: for every batch-norm of those networks and modes, and with cross-replica statistics on,
+the record matches a table recorded from the `vnet_bn_*` entries each batch-norm op launched in one eager step (and the all-reduces
+it made) before the choice moved into one function."""
 import pytest
 
 pytest.importorskip("torch")
@@ -327,3 +331,241 @@ def test_side_stream_guard_reads_the_launch_tag(monkeypatch, mode, op, layer, ta
     assert ops._side_stream("cuda", r, None, None, object(), sink) is None
     monkeypatch.setitem(ops._PROFILE, "only", {"conv k5 s1 64^3x1 32->32"})
     assert ops._side_stream("cuda", r, None, None, object(), sink) is side
+
+
+# (network, mode, cross-replica statistics) -> (op, M, C, bcast, x16, r16, epilogue, stats, stats16, apply16, allreduce) of every
+# distinct batch-norm of a step: its inputs -- op "act" (bn_act), "chain" (bn_chain), "stats" (a dead batch-norm's moving-average
+# update); rows M, channels C, tiled 1-channel input, x / residual bf16 (r16 None: no residual), x carries matching epilogue sums --
+# and the record its launches fix: statistics source and bf16-ness of the statistics and apply entries (a stats-only op launches no
+# apply: its tensors' dtype), and whether the backward all-reduced its sums (a backward without a data gradient -- the tiled image --
+# stops before that all-reduce: the statistics source decides).  Sync: two ranks over gloo.  C3 also in bf16 storage: the tiled
+# image's batch-norm.
+BN_EXPECTED = {
+    ('C3', 'fp32', False): [
+        ('act', 2097152, 16, True, False, None, False, 'stream', False, False, False),
+        ('act', 2097152, 16, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 262144, 32, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 262144, 32, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 32768, 64, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 32768, 64, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 4096, 128, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 4096, 128, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 512, 256, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 512, 256, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 4096, 128, False, False, None, False, 'stream', False, False, False),
+        ('stats', 4096, 128, False, False, None, True, 'epilogue', False, False, False),
+        ('chain', 4096, 128, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 32768, 64, False, False, None, False, 'stream', False, False, False),
+        ('stats', 32768, 64, False, False, None, True, 'epilogue', False, False, False),
+        ('chain', 32768, 64, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 262144, 32, False, False, None, False, 'stream', False, False, False),
+        ('chain', 262144, 32, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 2097152, 16, False, False, None, False, 'stream', False, False, False),
+        ('chain', 2097152, 16, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 2097152, 2, False, False, None, False, 'stream', False, False, False),
+    ],
+    ('C3', 'fp32_split3', False): [
+        ('act', 2097152, 16, True, False, None, False, 'stream', False, False, False),
+        ('act', 2097152, 16, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 262144, 32, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 262144, 32, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 32768, 64, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 32768, 64, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 4096, 128, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 4096, 128, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 512, 256, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 512, 256, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 4096, 128, False, False, None, False, 'stream', False, False, False),
+        ('stats', 4096, 128, False, False, None, True, 'epilogue', False, False, False),
+        ('chain', 4096, 128, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 32768, 64, False, False, None, False, 'stream', False, False, False),
+        ('stats', 32768, 64, False, False, None, True, 'epilogue', False, False, False),
+        ('chain', 32768, 64, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 262144, 32, False, False, None, False, 'stream', False, False, False),
+        ('chain', 262144, 32, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 2097152, 16, False, False, None, False, 'stream', False, False, False),
+        ('chain', 2097152, 16, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 2097152, 2, False, False, None, False, 'stream', False, False, False),
+    ],
+    ('C2', 'fp32', False): [
+        ('act', 524288, 16, True, False, None, False, 'stream', False, False, False),
+        ('act', 524288, 16, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 65536, 32, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 65536, 32, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 8192, 64, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 8192, 64, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 1024, 128, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 1024, 128, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 128, 256, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 128, 256, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 1024, 128, False, False, None, False, 'stream', False, False, False),
+        ('stats', 1024, 128, False, False, None, True, 'epilogue', False, False, False),
+        ('chain', 1024, 128, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 8192, 64, False, False, None, False, 'stream', False, False, False),
+        ('stats', 8192, 64, False, False, None, True, 'epilogue', False, False, False),
+        ('chain', 8192, 64, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 65536, 32, False, False, None, False, 'stream', False, False, False),
+        ('chain', 65536, 32, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 524288, 16, False, False, None, False, 'stream', False, False, False),
+        ('chain', 524288, 16, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 524288, 2, False, False, None, False, 'stream', False, False, False),
+    ],
+    ('C2', 'fp32_split3', False): [
+        ('act', 524288, 16, True, False, None, False, 'stream', False, False, False),
+        ('act', 524288, 16, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 65536, 32, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 65536, 32, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 8192, 64, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 8192, 64, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 1024, 128, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 1024, 128, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 128, 256, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 128, 256, False, False, False, True, 'epilogue', False, False, False),
+        ('act', 1024, 128, False, False, None, False, 'stream', False, False, False),
+        ('stats', 1024, 128, False, False, None, True, 'epilogue', False, False, False),
+        ('chain', 1024, 128, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 8192, 64, False, False, None, False, 'stream', False, False, False),
+        ('stats', 8192, 64, False, False, None, True, 'epilogue', False, False, False),
+        ('chain', 8192, 64, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 65536, 32, False, False, None, False, 'stream', False, False, False),
+        ('chain', 65536, 32, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 524288, 16, False, False, None, False, 'stream', False, False, False),
+        ('chain', 524288, 16, False, False, None, True, 'epilogue', False, False, False),
+        ('act', 524288, 2, False, False, None, False, 'stream', False, False, False),
+    ],
+    ('C5', 'bf16', False): [
+        ('act', 2097152, 16, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 2097152, 16, False, True, True, True, 'epilogue', False, True, False),
+        ('act', 262144, 32, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 262144, 32, False, True, True, True, 'epilogue', False, True, False),
+        ('act', 32768, 64, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 32768, 64, False, True, True, True, 'epilogue', False, True, False),
+        ('act', 4096, 128, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 4096, 128, False, True, True, True, 'epilogue', False, True, False),
+        ('act', 512, 256, False, True, None, True, 'small', True, True, False),
+        ('act', 512, 256, False, True, True, True, 'small', True, True, False),
+        ('act', 4096, 128, False, True, None, False, 'stream', True, True, False),
+        ('stats', 4096, 128, False, True, None, True, 'epilogue', False, True, False),
+        ('chain', 4096, 128, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 32768, 64, False, True, None, False, 'stream', True, True, False),
+        ('stats', 32768, 64, False, True, None, True, 'epilogue', False, True, False),
+        ('chain', 32768, 64, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 262144, 32, False, True, None, False, 'stream', True, True, False),
+        ('chain', 262144, 32, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 2097152, 16, False, True, None, False, 'stream', True, True, False),
+        ('chain', 2097152, 16, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 2097152, 5, False, False, None, False, 'stream', False, False, False),
+    ],
+    ('C3', 'bf16', False): [
+        ('act', 2097152, 16, True, False, None, False, 'stream', False, True, False),
+        ('act', 2097152, 16, False, True, True, True, 'epilogue', False, True, False),
+        ('act', 262144, 32, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 262144, 32, False, True, True, True, 'epilogue', False, True, False),
+        ('act', 32768, 64, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 32768, 64, False, True, True, True, 'epilogue', False, True, False),
+        ('act', 4096, 128, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 4096, 128, False, True, True, True, 'epilogue', False, True, False),
+        ('act', 512, 256, False, True, None, True, 'small', True, True, False),
+        ('act', 512, 256, False, True, True, True, 'small', True, True, False),
+        ('act', 4096, 128, False, True, None, False, 'stream', True, True, False),
+        ('stats', 4096, 128, False, True, None, True, 'epilogue', False, True, False),
+        ('chain', 4096, 128, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 32768, 64, False, True, None, False, 'stream', True, True, False),
+        ('stats', 32768, 64, False, True, None, True, 'epilogue', False, True, False),
+        ('chain', 32768, 64, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 262144, 32, False, True, None, False, 'stream', True, True, False),
+        ('chain', 262144, 32, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 2097152, 16, False, True, None, False, 'stream', True, True, False),
+        ('chain', 2097152, 16, False, True, None, True, 'epilogue', False, True, False),
+        ('act', 2097152, 2, False, False, None, False, 'stream', False, False, False),
+    ],
+    ('C2', 'fp32', True): [
+        ('act', 524288, 16, True, False, None, False, 'moments', False, False, True),
+        ('act', 524288, 16, False, False, False, False, 'moments', False, False, True),
+        ('act', 65536, 32, False, False, None, False, 'moments', False, False, True),
+        ('act', 65536, 32, False, False, False, False, 'moments', False, False, True),
+        ('act', 8192, 64, False, False, None, False, 'moments', False, False, True),
+        ('act', 8192, 64, False, False, False, False, 'moments', False, False, True),
+        ('act', 1024, 128, False, False, None, False, 'moments', False, False, True),
+        ('act', 1024, 128, False, False, False, False, 'moments', False, False, True),
+        ('act', 128, 256, False, False, None, False, 'moments', False, False, True),
+        ('act', 128, 256, False, False, False, False, 'moments', False, False, True),
+        ('stats', 1024, 128, False, False, None, False, 'moments', False, False, False),
+        ('chain', 1024, 128, False, False, None, False, 'moments', False, False, True),
+        ('stats', 8192, 64, False, False, None, False, 'moments', False, False, False),
+        ('chain', 8192, 64, False, False, None, False, 'moments', False, False, True),
+        ('chain', 65536, 32, False, False, None, False, 'moments', False, False, True),
+        ('act', 524288, 16, False, False, None, False, 'moments', False, False, True),
+        ('chain', 524288, 16, False, False, None, False, 'moments', False, False, True),
+        ('act', 524288, 2, False, False, None, False, 'moments', False, False, True),
+    ],
+    ('C5', 'bf16', True): [
+        ('act', 2097152, 16, False, True, None, False, 'moments', True, True, True),
+        ('act', 2097152, 16, False, True, True, False, 'moments', True, True, True),
+        ('act', 262144, 32, False, True, None, False, 'moments', True, True, True),
+        ('act', 262144, 32, False, True, True, False, 'moments', True, True, True),
+        ('act', 32768, 64, False, True, None, False, 'moments', True, True, True),
+        ('act', 32768, 64, False, True, True, False, 'moments', True, True, True),
+        ('act', 4096, 128, False, True, None, False, 'moments', True, True, True),
+        ('act', 4096, 128, False, True, True, False, 'moments', True, True, True),
+        ('act', 512, 256, False, True, None, False, 'moments', True, True, True),
+        ('act', 512, 256, False, True, True, False, 'moments', True, True, True),
+        ('stats', 4096, 128, False, True, None, False, 'moments', True, True, False),
+        ('chain', 4096, 128, False, True, None, False, 'moments', True, True, True),
+        ('stats', 32768, 64, False, True, None, False, 'moments', True, True, False),
+        ('chain', 32768, 64, False, True, None, False, 'moments', True, True, True),
+        ('chain', 262144, 32, False, True, None, False, 'moments', True, True, True),
+        ('chain', 2097152, 16, False, True, None, False, 'moments', True, True, True),
+        ('act', 2097152, 5, False, False, None, False, 'moments', False, False, True),
+    ],
+    ('C3', 'bf16', True): [
+        ('act', 2097152, 16, True, False, None, False, 'moments', False, True, True),
+        ('act', 2097152, 16, False, True, True, False, 'moments', True, True, True),
+        ('act', 262144, 32, False, True, None, False, 'moments', True, True, True),
+        ('act', 262144, 32, False, True, True, False, 'moments', True, True, True),
+        ('act', 32768, 64, False, True, None, False, 'moments', True, True, True),
+        ('act', 32768, 64, False, True, True, False, 'moments', True, True, True),
+        ('act', 4096, 128, False, True, None, False, 'moments', True, True, True),
+        ('act', 4096, 128, False, True, True, False, 'moments', True, True, True),
+        ('act', 512, 256, False, True, None, False, 'moments', True, True, True),
+        ('act', 512, 256, False, True, True, False, 'moments', True, True, True),
+        ('stats', 4096, 128, False, True, None, False, 'moments', True, True, False),
+        ('chain', 4096, 128, False, True, None, False, 'moments', True, True, True),
+        ('stats', 32768, 64, False, True, None, False, 'moments', True, True, False),
+        ('chain', 32768, 64, False, True, None, False, 'moments', True, True, True),
+        ('chain', 262144, 32, False, True, None, False, 'moments', True, True, True),
+        ('act', 2097152, 16, False, True, None, False, 'moments', True, True, True),
+        ('chain', 2097152, 16, False, True, None, False, 'moments', True, True, True),
+        ('act', 2097152, 2, False, False, None, False, 'moments', False, False, True),
+    ],
+}
+
+
+@pytest.mark.parametrize("net,mode,sync", sorted(BN_EXPECTED))
+def test_bn_routes_of_the_bench_networks(net, mode, sync):
+    for op, M, C, bcast, x16, r16, epilogue, *want in BN_EXPECTED[(net, mode, sync)]:
+        rt = ops.bn_route(op, M, C, bcast, x16, r16, epilogue, store16=mode == "bf16", sync=sync)
+        assert tuple(rt) == tuple(want), (op, M, C, bcast, x16, r16, epilogue)
+
+
+@pytest.mark.parametrize("args,kw,want", [
+    (("act", 512, 256), dict(x16=True, epilogue=True), ("small", True, True, False)),       # small before the epilogue sums
+    (("act", 512, 256), dict(x16=True, r16=False), ("stream", True, True, False)),          # fp32 residual (the forward refuses it)
+    (("chain", 512, 256), dict(x16=True), ("stream", True, True, False)),                   # chains and dead batch-norms: never small
+    (("stats", 512, 256), dict(x16=True, epilogue=True), ("epilogue", False, True, False)),
+    (("act", 4096, 128), dict(x16=True, epilogue=True, sync=True), ("moments", True, True, True)),
+    (("act", 4096, 16, True), dict(epilogue=True), ("stream", False, False, False)),        # (a tiled image carries no epilogue sums)
+    (("act", 4096, 16, True), dict(store16=True), ("stream", False, True, False)),          # tiled image, bf16 storage: fp32 statistics
+    (("act", 4096, 5, True), dict(store16=True), ("stream", False, False, False)),           # ... bf16 apply only for C = 8 * 2^k
+])
+def test_bn_route_precedence(args, kw, want):
+    kw = dict(dict(store16=False, sync=False), **kw)
+    assert tuple(ops.bn_route(*args, **kw)) == want
+
+
+def test_bn_route_small_lever(monkeypatch):
+    monkeypatch.setitem(ops._SMALL_BN, "on", False)
+    assert tuple(ops.bn_route("act", 512, 256, x16=True, epilogue=True, store16=True, sync=False)) == ("epilogue", False, True, False)
+    monkeypatch.setitem(ops._SMALL_BN, "on", True)
+    monkeypatch.setitem(ops._SMALL_BN, "rows", 256)
+    assert tuple(ops.bn_route("act", 512, 256, x16=True, store16=True, sync=False)) == ("stream", True, True, False)

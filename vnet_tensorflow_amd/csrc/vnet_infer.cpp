@@ -249,6 +249,21 @@ private:
         ABI_OK(vnet_pack_weights(mode, var(wname).dev, wp, taps, I, O, st_));
         return packed_[key] = wp;          // inference: filters never change, pack once
     }
+    // statistics of x (+ res) -- the bf16 kernels on a bf16 tensor, else the fp32 ones (tile: the 1-channel image broadcast to C) --
+    // then y = act(scale * xhat + shift), a bf16 tensor when y16; coef(mean, invstd) runs between the two (the chain's coefficients)
+    template <class Coef>
+    Tensor bn_apply(const Tensor& x, const Tensor* res, bool tile, bool y16, int C, const float* scale, const float* shift, int act,
+                    const float* alpha, Coef coef) {
+        Tensor y = y16 ? alloc16(x.B, x.D, x.H, x.W, C) : alloc(x.B, x.D, x.H, x.W, C);
+        float* mean = stat_; float* invstd = stat_ + 1024;
+        if (x.q) ABI_OK(vnet_bn_stats_b16(x.q, res ? res->q : nullptr, x.rows(), C, 1e-3f, 0.99f, mean, invstd, nullptr, nullptr, ws_, ws_bytes_, st_));
+        else ABI_OK(vnet_bn_stats(x.p, res ? res->p : nullptr, tile ? 1 : 0, x.rows(), C, 1e-3f, 0.99f, mean, invstd, nullptr, nullptr, ws_, ws_bytes_, st_));
+        coef(mean, invstd);
+        if (y16) ABI_OK(vnet_bn_act_fwd_b16(x.q ? x.q : (const void*)x.p, res ? res->q : nullptr, tile ? 1 : 0, x.rows(), C, mean, invstd, scale, shift,
+                                            act, alpha, y.q, st_));
+        else ABI_OK(vnet_bn_act_fwd(x.p, res ? res->p : nullptr, tile ? 1 : 0, x.rows(), C, mean, invstd, scale, shift, act, alpha, y.p, st_));
+        return y;
+    }
     // tf.layers.batch_normalization(training=True) [+ residual] [+ tile] + activation; alpha lives in the enclosing scope
     Tensor bn(const Tensor& x, int act, const Tensor* res, bool tile) {
         const std::string sc = scope();
@@ -256,30 +271,20 @@ private:
         const std::string name = sc + "/batch_normalization" + (n ? "_" + std::to_string(n) : "");
         Var& g = var(name + "/gamma"); Var& b = var(name + "/beta");
         const int C = (int)g.n;
-        float* mean = stat_; float* invstd = stat_ + 1024;
         const float* alpha = act == VNET_ACT_PRELU ? var(sc + "/alpha").dev : nullptr;
-        if (cfg.store16 && (x.q || tile)) {
-            // bf16 storage: statistics of the bf16 tensor (+ bf16 residual) -- or of the fp32 1-channel image that is tiled -- in fp32,
-            // one rounding of the normalised / activated value
+        // bf16 storage: statistics of the bf16 tensor (+ bf16 residual) -- or of the fp32 1-channel image that is tiled -- in fp32,
+        // one rounding of the normalised / activated value
+        const bool y16 = cfg.store16 && (x.q || tile);
+        // tiny tensors: one launch -- the Python path's rule (ops._SMALL_BN: on, <= 512 rows)
+        constexpr bool small_on = true;
+        constexpr long small_rows = 512;
+        if (y16 && !tile && small_on && (long)x.rows() <= small_rows && vnet_bn_small_ok(x.rows(), C)) {
             Tensor y = alloc16(x.B, x.D, x.H, x.W, C);
-            // tiny tensors: one launch -- the Python path's rule (ops._SMALL_BN: on, <= 512 rows)
-            constexpr bool small_on = true;
-            constexpr long small_rows = 512;
-            if (!tile && small_on && (long)x.rows() <= small_rows && vnet_bn_small_ok(x.rows(), C)) {
-                ABI_OK(vnet_bn_small_fwd_b16(x.q, res ? res->q : nullptr, x.rows(), C, 1e-3f, 0.99f, g.dev, b.dev, act, alpha, mean, invstd,
-                                             nullptr, nullptr, y.q, st_));
-                return y;
-            }
-            if (tile) ABI_OK(vnet_bn_stats(x.p, nullptr, 1, x.rows(), C, 1e-3f, 0.99f, mean, invstd, nullptr, nullptr, ws_, ws_bytes_, st_));
-            else ABI_OK(vnet_bn_stats_b16(x.q, res ? res->q : nullptr, x.rows(), C, 1e-3f, 0.99f, mean, invstd, nullptr, nullptr, ws_, ws_bytes_, st_));
-            ABI_OK(vnet_bn_act_fwd_b16(tile ? (const void*)x.p : x.q, res ? res->q : nullptr, tile ? 1 : 0, x.rows(), C, mean, invstd, g.dev, b.dev,
-                                       act, alpha, y.q, st_));
+            ABI_OK(vnet_bn_small_fwd_b16(x.q, res ? res->q : nullptr, x.rows(), C, 1e-3f, 0.99f, g.dev, b.dev, act, alpha, stat_, stat_ + 1024,
+                                         nullptr, nullptr, y.q, st_));
             return y;
         }
-        Tensor y = alloc(x.B, x.D, x.H, x.W, C);
-        ABI_OK(vnet_bn_stats(x.p, res ? res->p : nullptr, tile ? 1 : 0, x.rows(), C, 1e-3f, 0.99f, mean, invstd, nullptr, nullptr, ws_, ws_bytes_, st_));
-        ABI_OK(vnet_bn_act_fwd(x.p, res ? res->p : nullptr, tile ? 1 : 0, x.rows(), C, mean, invstd, g.dev, b.dev, act, alpha, y.p, st_));
-        return y;
+        return bn_apply(x, res, tile, y16, C, g.dev, b.dev, act, alpha, [](const float*, const float*) {});
     }
     // the decoder's batch-norm chains in closed form (include/vnet_hip.h, vnet_bn_chain_coef_fwd): one fused normalisation of x
     //   kind 0: x = BN(x); r = BN(x); out = prelu(BN(x + r))      kind 1: r = BN(x); out = prelu(BN(x + r))
@@ -294,21 +299,12 @@ private:
             Var& g = var(name + "/gamma"); Var& b = var(name + "/beta");
             gp[k] = g.dev; bp[k] = b.dev; C = (int)g.n;
         }
-        float* mean = stat_; float* invstd = stat_ + 1024; float* ceff = stat_ + 2048; float* deff = stat_ + 3072;
-        if (x.q) {
-            Tensor y = alloc16(x.B, x.D, x.H, x.W, C);
-            ABI_OK(vnet_bn_stats_b16(x.q, nullptr, x.rows(), C, 1e-3f, 0.99f, mean, invstd, nullptr, nullptr, ws_, ws_bytes_, st_));
-            ABI_OK(vnet_bn_chain_coef_fwd(kind, C, 1e-3f, 0.99f, mean, invstd, gp[0], bp[0], gp[1], bp[1], gp[2], bp[2], ceff, deff,
-                                          nullptr, nullptr, nullptr, nullptr, st_));
-            ABI_OK(vnet_bn_act_fwd_b16(x.q, nullptr, 0, x.rows(), C, mean, invstd, ceff, deff, VNET_ACT_PRELU, var(sc + "/alpha").dev, y.q, st_));
-            return y;
-        }
-        Tensor y = alloc(x.B, x.D, x.H, x.W, C);
-        ABI_OK(vnet_bn_stats(x.p, nullptr, 0, x.rows(), C, 1e-3f, 0.99f, mean, invstd, nullptr, nullptr, ws_, ws_bytes_, st_));
-        ABI_OK(vnet_bn_chain_coef_fwd(kind, C, 1e-3f, 0.99f, mean, invstd, gp[0], bp[0], gp[1], bp[1], gp[2], bp[2], ceff, deff,
-                                      nullptr, nullptr, nullptr, nullptr, st_));
-        ABI_OK(vnet_bn_act_fwd(x.p, nullptr, 0, x.rows(), C, mean, invstd, ceff, deff, VNET_ACT_PRELU, var(sc + "/alpha").dev, y.p, st_));
-        return y;
+        float* ceff = stat_ + 2048; float* deff = stat_ + 3072;
+        return bn_apply(x, nullptr, false, x.q != nullptr, C, ceff, deff, VNET_ACT_PRELU, var(sc + "/alpha").dev,
+                        [&](const float* mean, const float* invstd) {
+                            ABI_OK(vnet_bn_chain_coef_fwd(kind, C, 1e-3f, 0.99f, mean, invstd, gp[0], bp[0], gp[1], bp[1], gp[2], bp[2], ceff,
+                                                          deff, nullptr, nullptr, nullptr, nullptr, st_));
+                        });
     }
     // Cin_w: input channels of the FILTER when the tensor carries zero-padded channels (the cast 4-modality input), else 0
     Tensor conv(const Tensor& x0, const Tensor* x1, int ks, int stride, int Cout, int Cin_w = 0) {

@@ -151,13 +151,8 @@ def batch_normalization(x, activation=None, residual=None, tile=False, channels=
     fused with the optional residual add in front (x + residual), the tf.tile of a 1-channel
     input (tile=True) and the activation behind it.  Variables live under the auto-uniquified
     layer scope 'batch_normalization[_N]'; 'alpha' lives in the enclosing scope like the reference."""
-    store = current()
     C = int(channels if channels is not None else x.shape[-1])
-    with variable_scope(store.unique_layer_name("batch_normalization")):
-        gamma = get_variable('gamma', initializer=lambda: np.ones((C,), np.float32))
-        beta = get_variable('beta', initializer=lambda: np.zeros((C,), np.float32))
-        mm = get_variable('moving_mean', initializer=lambda: np.zeros((C,), np.float32), trainable=False)
-        mv = get_variable('moving_variance', initializer=lambda: np.ones((C,), np.float32), trainable=False)
+    gamma, beta, mm, mv = _bn_variables(C)
     if dead:
         ops.bn_update_only(x, C, mm, mv)
         return None

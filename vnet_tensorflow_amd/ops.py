@@ -1213,34 +1213,6 @@ def set_sync_batch_norm(group=None, enabled=True):
     _SYNC_BN = ((lambda t: dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)), world) if world > 1 else None
 
 
-def _bn_statistics(L, x, r, bcast, M, C, mean, invstd, mm, mv, ws, nb, pre=None, r_orig=None):
-    """mean/invstd (+ moving-average update) of s = x (+ r); returns the row count the statistics cover.
-    pre: _EpilogueStats the producing convolution attached to x (used when it covers exactly x + r)."""
-    if (_SYNC_BN is None and pre is not None and not bcast and pre.residual is r_orig and pre.partial.shape[1] == 2 * C):
-        check(L.vnet_bn_finalize_partial(_ptr(pre.partial), pre.rows, C, float(M), BN_EPS, BN_MOMENTUM, _ptr(mean), _ptr(invstd),
-                                         _ptr(mm), _ptr(mv), _stream()), "vnet_bn_finalize_partial")
-        return float(M)
-    x16 = _is16(x)
-    if _SYNC_BN is None:
-        if x16:
-            check(L.vnet_bn_stats_b16(_ptr(x), _ptr(r), M, C, BN_EPS, BN_MOMENTUM, _ptr(mean), _ptr(invstd),
-                                      _ptr(mm), _ptr(mv), _ptr(ws), nb, _stream()), "vnet_bn_stats_b16")
-        else:
-            check(L.vnet_bn_stats(_ptr(x), _ptr(r), int(bcast), M, C, BN_EPS, BN_MOMENTUM, _ptr(mean), _ptr(invstd),
-                                  _ptr(mm), _ptr(mv), _ptr(ws), nb, _stream()), "vnet_bn_stats")
-        return float(M)
-    all_reduce, world = _SYNC_BN
-    sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
-    if x16:
-        check(L.vnet_bn_moments_b16(_ptr(x), _ptr(r), M, C, _ptr(sums), _ptr(ws), nb, _stream()), "vnet_bn_moments_b16")
-    else:
-        check(L.vnet_bn_moments(_ptr(x), _ptr(r), int(bcast), M, C, _ptr(sums), _ptr(ws), nb, _stream()), "vnet_bn_moments")
-    all_reduce(sums)
-    check(L.vnet_bn_finalize(_ptr(sums), float(M) * world, C, BN_EPS, BN_MOMENTUM, _ptr(mean), _ptr(invstd),
-                             _ptr(mm), _ptr(mv), _stream()), "vnet_bn_finalize")
-    return float(M) * world
-
-
 # bf16 storage, tiny tensors (the 8^3 level: <= 512 rows): statistics + finalize + normalise in ONE launch, and reduce + finalize +
 # apply in one (vnet_bn_small_*_b16; `_SMALL_BN["on"] = False`: the streaming kernels everywhere).  Measured (profiles/ab_env.sh, C5 step):
 # <= 512 rows -0.015 ms, <= 1024 the same, <= 8192 (the 16^3 level too) +0.13 ms -- one workgroup per channel octet uses 16 bytes
@@ -1248,9 +1220,95 @@ def _bn_statistics(L, x, r, bcast, M, C, mean, invstd, mm, mv, ws, nb, pre=None,
 _SMALL_BN = {"on": True, "rows": 512}
 
 
-def _bn_small(M, C, *tensors):
-    return (_SMALL_BN["on"] and M <= _SMALL_BN["rows"] and _SYNC_BN is None and all(t is None or _is16(t) for t in tensors)
-            and bool(_lib.lib().vnet_bn_small_ok(int(M), int(C))))
+class BnRoute(collections.namedtuple("BnRoute", "stats stats16 apply16 allreduce")):
+    """How one batch-norm runs, as bn_route() chose it.  stats: where mean / invstd come from -- "epilogue" (finalize the partial
+    sums the producing convolution wrote), "stream" (a statistics pass over x (+ r)), "moments" (raw moments all-reduced over the
+    replicas, then finalize) or "small" (the one-launch bf16 kernels, forward and backward); stats16 / apply16: the statistics
+    kernels / the normalise and backward kernels are the bf16-storage (`_b16`) entries; allreduce: the backward all-reduces its sums
+    [sum_dz | sum_dz_xhat] before the apply."""
+    __slots__ = ()
+
+
+def bn_route(op, M, C, bcast=False, x16=False, r16=None, epilogue=False, store16=None, sync=None):
+    """The kernels of batch-norm `op` ("act": bn_act, "chain": bn_chain, "stats": the moving-average update of a dead batch-norm)
+    over s = x (+ r), M rows of C channels.  bcast: x has one channel, tiled to C; x16 / r16: x / the residual is bf16 (r16 None: no
+    residual); epilogue: x carries its producer's partial sums of exactly s (_epilogue_of); store16: bf16-storage mode; sync:
+    cross-replica statistics (store16 / sync None: the current setting)."""
+    store16 = _COMPUTE["store16"] if store16 is None else store16
+    sync = _SYNC_BN is not None if sync is None else sync
+    # (tried before the epilogue sums, which it does not use; per-replica only)
+    if (op == "act" and not bcast and x16 and r16 is not False and not sync and _SMALL_BN["on"] and M <= _SMALL_BN["rows"]
+            and _lib.lib().vnet_bn_small_ok(int(M), int(C))):
+        return BnRoute("small", True, True, False)
+    stats = "moments" if sync else "epilogue" if epilogue and not bcast else "stream"
+    # bf16 storage: a bf16 input, or the tiled fp32 1-channel image in that mode (C = 8 * 2^k; the 2..5-class batch-norm of the
+    # logits stays on the fp32 kernels).  The image's statistics stay on the fp32 kernels.
+    apply16 = x16 or (bcast and store16 and C % 8 == 0)
+    return BnRoute(stats, x16 and stats != "epilogue", apply16, sync and op != "stats")
+
+
+def _epilogue_of(x, r, C):
+    """The _EpilogueStats the producing convolution attached to x when they cover exactly x + r (r: the same object) over C
+    channels, else None."""
+    pre = getattr(x, "_vnet_stats", None)
+    return pre if pre is not None and pre.residual is r and pre.partial.shape[1] == 2 * C else None
+
+
+def _bn_stats(rt, x, r, bcast, M, C, mm, mv, pre=None):
+    """mean / invstd (+ the moving-average update) of s = x (+ r) the way route rt says (pre: _epilogue_of x); returns mean, invstd
+    and the row count they cover."""
+    L = _lib.lib()
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    invstd = torch.empty(C, dtype=torch.float32, device=x.device)
+    nb = L.vnet_bn_ws_bytes(C)
+    ws = workspace(nb, x.device)
+    if rt.stats == "epilogue":
+        check(L.vnet_bn_finalize_partial(_ptr(pre.partial), pre.rows, C, float(M), BN_EPS, BN_MOMENTUM, _ptr(mean), _ptr(invstd),
+                                         _ptr(mm), _ptr(mv), _stream()), "vnet_bn_finalize_partial")
+        return mean, invstd, float(M)
+    sfx, tile = ("_b16", ()) if rt.stats16 else ("", (int(bcast),))       # (the bf16 statistics kernels take no tile flag)
+    if rt.stats == "stream":
+        name = "vnet_bn_stats" + sfx
+        check(getattr(L, name)(_ptr(x), _ptr(r), *tile, M, C, BN_EPS, BN_MOMENTUM, _ptr(mean), _ptr(invstd), _ptr(mm), _ptr(mv),
+                               _ptr(ws), nb, _stream()), name)
+        return mean, invstd, float(M)
+    all_reduce, world = _SYNC_BN
+    sums = torch.empty(2 * C, dtype=torch.float64, device=x.device)
+    name = "vnet_bn_moments" + sfx
+    check(getattr(L, name)(_ptr(x), _ptr(r), *tile, M, C, _ptr(sums), _ptr(ws), nb, _stream()), name)
+    all_reduce(sums)
+    check(L.vnet_bn_finalize(_ptr(sums), float(M) * world, C, BN_EPS, BN_MOMENTUM, _ptr(mean), _ptr(invstd),
+                             _ptr(mm), _ptr(mv), _stream()), "vnet_bn_finalize")
+    return mean, invstd, float(M) * world
+
+
+def _bn_backward(rt, dy, x, r, bcast, M, C, mean, invstd, scale, shift, act, alpha, dscale, dshift, dalpha, ds, m_total,
+                 all_reduce=None, coef=None):
+    """Backward of y = act(scale * xhat + shift), xhat the normalised s = x (+ r): the sums sum_dz_xhat -> dscale, sum_dz -> dshift
+    (and dalpha), all-reduced when rt says so, then ds (None: no data gradient) from them.  coef(sum_dz_xhat) runs between the two
+    and returns the apply's xhat coefficient (the chain's vnet_bn_chain_coef_bwd)."""
+    L = _lib.lib()
+    nb = L.vnet_bn_ws_bytes(C)
+    ws = workspace(nb, dy.device)
+    if rt.stats == "small":
+        check(L.vnet_bn_small_bwd_b16(_ptr(dy), _ptr(x), _ptr(r), M, C, _ptr(mean), _ptr(invstd), _ptr(scale), _ptr(shift), act,
+                                      _ptr(alpha), _ptr(dscale), _ptr(dshift), _ptr(dalpha), _ptr(ds), _stream()), "vnet_bn_small_bwd_b16")
+        return
+    sfx = "_b16" if rt.apply16 else ""
+    args = (_ptr(dy), _ptr(x), _ptr(r), int(bcast), M, C, _ptr(mean), _ptr(invstd), _ptr(scale), _ptr(shift), act, _ptr(alpha))
+    name = "vnet_bn_act_bwd_reduce" + sfx
+    check(getattr(L, name)(*args, _ptr(dscale), _ptr(dshift), _ptr(dalpha), _ptr(ws), nb, _stream()), name)
+    sdz, sdzx = dshift, dscale
+    if rt.allreduce and (ds is not None or coef is not None):
+        # this replica's parameter gradients stay local (the gradient all-reduce averages them); the data gradient needs the sums
+        # over the whole cross-replica batch
+        sdz = torch.cat([dshift.reshape(-1), dscale.reshape(-1)])
+        all_reduce(sdz)
+        sdzx = sdz[C:]
+    extra = coef(sdzx) if coef is not None else None
+    if ds is not None:
+        name = "vnet_bn_act_bwd_apply" + sfx
+        check(getattr(L, name)(*args, _ptr(sdz), _ptr(sdzx), m_total, _ptr(extra), _ptr(ds), _stream()), name)
 
 
 class _BnActFn(torch.autograd.Function):
@@ -1258,43 +1316,27 @@ class _BnActFn(torch.autograd.Function):
     def forward(ctx, x, r, gamma, beta, alpha, act, bcast, mm, mv):
         L = _lib.lib()
         ctx.slot_r = getattr(r, "_vnet_slot", None)
-        pre, r_orig = getattr(x, "_vnet_stats", None), r
+        C = gamma.numel()
+        pre = _epilogue_of(x, r, C)
         x = x.contiguous()
         r = r.contiguous() if r is not None else None
-        C = gamma.numel()
         M = x.numel() if bcast else x.numel() // C
-        dev = x.device
-        mean = torch.empty(C, dtype=torch.float32, device=dev)
-        invstd = torch.empty(C, dtype=torch.float32, device=dev)
-        ctx.small = small = (not bcast) and _is16(x) and _bn_small(M, C, x, r)
-        if small:
-            y = torch.empty(x.shape[:-1] + (C,), dtype=torch.bfloat16, device=dev)
+        ctx.rt = rt = bn_route("act", M, C, bcast, _is16(x), None if r is None else _is16(r), pre is not None)
+        if rt.apply16 and r is not None and not _is16(r):
+            raise VnetHipError("bn_act: bf16 and float32 tensors mixed")
+        y = torch.empty(x.shape[:-1] + (C,), dtype=torch.bfloat16 if rt.apply16 else torch.float32, device=x.device)
+        if rt.stats == "small":
+            mean = torch.empty(C, dtype=torch.float32, device=x.device)
+            invstd = torch.empty(C, dtype=torch.float32, device=x.device)
             check(L.vnet_bn_small_fwd_b16(_ptr(x), _ptr(r), M, C, BN_EPS, BN_MOMENTUM, _ptr(gamma), _ptr(beta), act, _ptr(alpha),
                                           _ptr(mean), _ptr(invstd), _ptr(mm), _ptr(mv), _ptr(y), _stream()), "vnet_bn_small_fwd_b16")
-            ctx.m_total, ctx.sync, ctx.b16 = float(M), None, True
-            ctx.save_for_backward(x, r, gamma, beta, alpha, mean, invstd)
-            ctx.params = (gamma, beta, alpha)
-            ctx.cfg = (act, bcast, M, C)
-            ctx.mark_non_differentiable(mean, invstd)
-            ctx.set_materialize_grads(False)
-            return y, mean, invstd
-        nb = L.vnet_bn_ws_bytes(C)
-        ws = workspace(nb, dev)
-        ctx.m_total = _bn_statistics(L, x, r, bcast, M, C, mean, invstd, mm, mv, ws, nb, pre, r_orig)
-        ctx.sync = _SYNC_BN
-        # bf16-storage: a bf16 input, or the tiled fp32 1-channel image in that mode (C = 8 * 2^k; the 2..5-class batch-norm of the
-        # logits stays on the fp32 kernels)
-        ctx.b16 = b16 = _is16(x) or (bcast and _COMPUTE["store16"] and C % 8 == 0)
-        if b16:
-            if r is not None and not _is16(r):
-                raise VnetHipError("bn_act: bf16 and float32 tensors mixed")
-            y = torch.empty(x.shape[:-1] + (C,), dtype=torch.bfloat16, device=dev)
-            check(L.vnet_bn_act_fwd_b16(_ptr(x), _ptr(r), int(bcast), M, C, _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta),
-                                        act, _ptr(alpha), _ptr(y), _stream()), "vnet_bn_act_fwd_b16")
+            ctx.m_total = float(M)
         else:
-            y = torch.empty(x.shape[:-1] + (C,), dtype=torch.float32, device=dev)
-            check(L.vnet_bn_act_fwd(_ptr(x), _ptr(r), int(bcast), M, C, _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta),
-                                    act, _ptr(alpha), _ptr(y), _stream()), "vnet_bn_act_fwd")
+            mean, invstd, ctx.m_total = _bn_stats(rt, x, r, bcast, M, C, mm, mv, pre)
+            name = "vnet_bn_act_fwd" + ("_b16" if rt.apply16 else "")
+            check(getattr(L, name)(_ptr(x), _ptr(r), int(bcast), M, C, _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta),
+                                   act, _ptr(alpha), _ptr(y), _stream()), name)
+        ctx.all_reduce = _SYNC_BN[0] if rt.allreduce else None
         ctx.save_for_backward(x, r, gamma, beta, alpha, mean, invstd)
         ctx.params = (gamma, beta, alpha)
         ctx.cfg = (act, bcast, M, C)
@@ -1304,59 +1346,19 @@ class _BnActFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, _gmean, _ginvstd):
-        L = _lib.lib()
         x, r, gamma, beta, alpha, mean, invstd = ctx.saved_tensors
         act, bcast, M, C = ctx.cfg
         dy = dy.contiguous()
-        dev = dy.device
+        if ctx.rt.apply16 and not _is16(dy):
+            raise VnetHipError("bn_act backward: expected a bfloat16 gradient")
         gref, bref, aref = ctx.params
         dgamma, sg = _grad_out(gref)
         dbeta, sbt = _grad_out(bref)
         dalpha, sa = _grad_out(aref) if alpha is not None else (None, None)
         need_ds = ctx.needs_input_grad[0] or (r is not None and ctx.needs_input_grad[1])
-        if ctx.b16:
-            ds = torch.empty(dy.shape, dtype=torch.bfloat16, device=dev) if need_ds else None
-        else:
-            ds = torch.empty(dy.shape, dtype=torch.float32, device=dev) if need_ds else None
-        nb = L.vnet_bn_ws_bytes(C)
-        ws = workspace(nb, dev)
-        if ctx.small:
-            if not _is16(dy):
-                raise VnetHipError("bn_act backward: expected a bfloat16 gradient")
-            check(L.vnet_bn_small_bwd_b16(_ptr(dy), _ptr(x), _ptr(r), M, C, _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), act,
-                                          _ptr(alpha), _ptr(dgamma), _ptr(dbeta), _ptr(dalpha), _ptr(ds), _stream()), "vnet_bn_small_bwd_b16")
-        elif ctx.b16:
-            if not _is16(dy):
-                raise VnetHipError("bn_act backward: expected a bfloat16 gradient")
-            check(L.vnet_bn_act_bwd_reduce_b16(_ptr(dy), _ptr(x), _ptr(r), int(bcast), M, C, _ptr(mean), _ptr(invstd),
-                                               _ptr(gamma), _ptr(beta), act, _ptr(alpha), _ptr(dgamma), _ptr(dbeta),
-                                               _ptr(dalpha), _ptr(ws), nb, _stream()), "vnet_bn_act_bwd_reduce_b16")
-            if ds is not None:
-                if ctx.sync is None:
-                    sdz, sdzx = dbeta, dgamma
-                else:
-                    tot = torch.cat([dbeta.reshape(-1), dgamma.reshape(-1)])
-                    ctx.sync[0](tot)
-                    sdz, sdzx = tot, tot[C:]
-                check(L.vnet_bn_act_bwd_apply_b16(_ptr(dy), _ptr(x), _ptr(r), int(bcast), M, C, _ptr(mean), _ptr(invstd),
-                                                  _ptr(gamma), _ptr(beta), act, _ptr(alpha), _ptr(sdz), _ptr(sdzx),
-                                                  ctx.m_total, None, _ptr(ds), _stream()), "vnet_bn_act_bwd_apply_b16")
-        elif ctx.sync is None:
-            check(L.vnet_bn_act_bwd(_ptr(dy), _ptr(x), _ptr(r), int(bcast), M, C, _ptr(mean), _ptr(invstd), _ptr(gamma),
-                                    _ptr(beta), act, _ptr(alpha), _ptr(dgamma), _ptr(dbeta), _ptr(dalpha), _ptr(ds),
-                                    _ptr(ws), nb, _stream()), "vnet_bn_act_bwd")
-        else:
-            # this replica's parameter gradients stay local (the gradient all-reduce averages them);
-            # the data gradient needs the sums over the whole cross-replica batch
-            check(L.vnet_bn_act_bwd_reduce(_ptr(dy), _ptr(x), _ptr(r), int(bcast), M, C, _ptr(mean), _ptr(invstd),
-                                           _ptr(gamma), _ptr(beta), act, _ptr(alpha), _ptr(dgamma), _ptr(dbeta),
-                                           _ptr(dalpha), _ptr(ws), nb, _stream()), "vnet_bn_act_bwd_reduce")
-            if ds is not None:
-                tot = torch.cat([dbeta.reshape(-1), dgamma.reshape(-1)])
-                ctx.sync[0](tot)
-                check(L.vnet_bn_act_bwd_apply(_ptr(dy), _ptr(x), _ptr(r), int(bcast), M, C, _ptr(mean), _ptr(invstd),
-                                              _ptr(gamma), _ptr(beta), act, _ptr(alpha), _ptr(tot), _ptr(tot[C:]),
-                                              ctx.m_total, None, _ptr(ds), _stream()), "vnet_bn_act_bwd_apply")
+        ds = torch.empty(dy.shape, dtype=torch.bfloat16 if ctx.rt.apply16 else torch.float32, device=dy.device) if need_ds else None
+        _bn_backward(ctx.rt, dy, x, r, bcast, M, C, mean, invstd, gamma, beta, act, alpha, dgamma, dbeta, dalpha, ds, ctx.m_total,
+                     ctx.all_reduce)
         th = getattr(gref, "_vnet_deferred", None)
         if th is not None and sg is not None and sbt is not None:
             del gref._vnet_deferred
@@ -1377,32 +1379,24 @@ class _BnChainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, kind, act, alpha, g1, b1, g2, b2, g3, b3, bufs):
         L = _lib.lib()
-        pre = getattr(x, "_vnet_stats", None)
-        x = x.contiguous()
         C = g1.numel()
+        pre = _epilogue_of(x, None, C)
+        x = x.contiguous()
         M = x.numel() // C
         dev = x.device
         mm1, mv1, mm2, mv2, mm3, mv3 = bufs
-        mean = torch.empty(C, dtype=torch.float32, device=dev)
-        invstd = torch.empty(C, dtype=torch.float32, device=dev)
-        nb = L.vnet_bn_ws_bytes(C)
-        ws = workspace(nb, dev)
-        ctx.m_total = _bn_statistics(L, x, None, False, M, C, mean, invstd, mm1, mv1, ws, nb, pre, None)
-        ctx.sync = _SYNC_BN
+        ctx.rt = rt = bn_route("chain", M, C, x16=_is16(x), epilogue=pre is not None)
+        mean, invstd, ctx.m_total = _bn_stats(rt, x, None, False, M, C, mm1, mv1, pre)
+        ctx.all_reduce = _SYNC_BN[0] if rt.allreduce else None
         ceff = torch.empty(C, dtype=torch.float32, device=dev)
         deff = torch.empty(C, dtype=torch.float32, device=dev)
         check(L.vnet_bn_chain_coef_fwd(kind, C, BN_EPS, BN_MOMENTUM, _ptr(mean), _ptr(invstd), _ptr(g1), _ptr(b1), _ptr(g2), _ptr(b2),
                                        _ptr(g3), _ptr(b3), _ptr(ceff), _ptr(deff), _ptr(mm2), _ptr(mv2), _ptr(mm3), _ptr(mv3),
                                        _stream()), "vnet_bn_chain_coef_fwd")
-        ctx.b16 = _is16(x)
-        if ctx.b16:
-            y = torch.empty(x.shape, dtype=torch.bfloat16, device=dev)
-            check(L.vnet_bn_act_fwd_b16(_ptr(x), None, 0, M, C, _ptr(mean), _ptr(invstd), _ptr(ceff), _ptr(deff),
-                                        act, _ptr(alpha), _ptr(y), _stream()), "vnet_bn_act_fwd_b16")
-        else:
-            y = torch.empty(x.shape, dtype=torch.float32, device=dev)
-            check(L.vnet_bn_act_fwd(_ptr(x), None, 0, M, C, _ptr(mean), _ptr(invstd), _ptr(ceff), _ptr(deff),
-                                    act, _ptr(alpha), _ptr(y), _stream()), "vnet_bn_act_fwd")
+        y = torch.empty(x.shape, dtype=torch.bfloat16 if rt.apply16 else torch.float32, device=dev)
+        name = "vnet_bn_act_fwd" + ("_b16" if rt.apply16 else "")
+        check(getattr(L, name)(_ptr(x), None, 0, M, C, _ptr(mean), _ptr(invstd), _ptr(ceff), _ptr(deff), act, _ptr(alpha), _ptr(y),
+                               _stream()), name)
         ctx.save_for_backward(x, alpha, g1, g2, g3, mean, invstd, ceff, deff)
         ctx.params = (alpha, g1, b1, g2, b2, g3, b3)
         ctx.cfg = (kind, act, M, C)
@@ -1419,40 +1413,18 @@ class _BnChainFn(torch.autograd.Function):
         dC = torch.empty(C, dtype=torch.float32, device=dev)
         dD = torch.empty(C, dtype=torch.float32, device=dev)
         dalpha, sa = _grad_out(aref) if alpha is not None else (None, None)
-        nb = L.vnet_bn_ws_bytes(C)
-        ws = workspace(nb, dev)
-        if ctx.b16:
-            check(L.vnet_bn_act_bwd_reduce_b16(_ptr(dy), _ptr(x), None, 0, M, C, _ptr(mean), _ptr(invstd), _ptr(ceff), _ptr(deff),
-                                               act, _ptr(alpha), _ptr(dC), _ptr(dD), _ptr(dalpha), _ptr(ws), nb, _stream()),
-                  "vnet_bn_act_bwd_reduce_b16")
-        else:
-            check(L.vnet_bn_act_bwd_reduce(_ptr(dy), _ptr(x), None, 0, M, C, _ptr(mean), _ptr(invstd), _ptr(ceff), _ptr(deff),
-                                           act, _ptr(alpha), _ptr(dC), _ptr(dD), _ptr(dalpha), _ptr(ws), nb, _stream()),
-                  "vnet_bn_act_bwd_reduce")
-        if ctx.sync is None:
-            tot = None
-            dCg, dDg = dC, dD
-        else:                      # cross-replica statistics: the data gradient needs the sums over every replica
-            tot = torch.cat([dD, dC])
-            ctx.sync[0](tot)
-            dDg, dCg = tot[:C], tot[C:]
         outs = [_grad_out(r) if r is not None else (None, None) for r in (g1r, b1r, g2r, b2r, g3r, b3r)]
         (dg1, s1), (db1, t1), (dg2, s2), (db2, t2), (dg3, s3), (db3, t3) = outs
         extra = torch.empty(C, dtype=torch.float32, device=dev)
-        check(L.vnet_bn_chain_coef_bwd(kind, C, BN_EPS, ctx.m_total, _ptr(mean), _ptr(invstd), _ptr(g1), _ptr(g2), _ptr(g3),
-                                       _ptr(dC), _ptr(dD), _ptr(dCg), _ptr(dg1), _ptr(db1), _ptr(dg2), _ptr(db2), _ptr(dg3), _ptr(db3),
-                                       _ptr(extra), _stream()), "vnet_bn_chain_coef_bwd")
-        dx = None
-        if ctx.needs_input_grad[0] and ctx.b16:
-            dx = torch.empty(dy.shape, dtype=torch.bfloat16, device=dev)
-            check(L.vnet_bn_act_bwd_apply_b16(_ptr(dy), _ptr(x), None, 0, M, C, _ptr(mean), _ptr(invstd), _ptr(ceff), _ptr(deff),
-                                              act, _ptr(alpha), _ptr(dDg), _ptr(dCg), ctx.m_total, _ptr(extra), _ptr(dx),
-                                              _stream()), "vnet_bn_act_bwd_apply_b16")
-        elif ctx.needs_input_grad[0]:
-            dx = torch.empty(dy.shape, dtype=torch.float32, device=dev)
-            check(L.vnet_bn_act_bwd_apply(_ptr(dy), _ptr(x), None, 0, M, C, _ptr(mean), _ptr(invstd), _ptr(ceff), _ptr(deff),
-                                          act, _ptr(alpha), _ptr(dDg), _ptr(dCg), ctx.m_total, _ptr(extra), _ptr(dx),
-                                          _stream()), "vnet_bn_act_bwd_apply")
+        dx = torch.empty(dy.shape, dtype=torch.bfloat16 if ctx.rt.apply16 else torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+
+        def coef(dCg):        # every gamma / beta gradient of the chain, and the xhat coefficient of the apply
+            check(L.vnet_bn_chain_coef_bwd(kind, C, BN_EPS, ctx.m_total, _ptr(mean), _ptr(invstd), _ptr(g1), _ptr(g2), _ptr(g3),
+                                           _ptr(dC), _ptr(dD), _ptr(dCg), _ptr(dg1), _ptr(db1), _ptr(dg2), _ptr(db2), _ptr(dg3),
+                                           _ptr(db3), _ptr(extra), _stream()), "vnet_bn_chain_coef_bwd")
+            return extra
+        _bn_backward(ctx.rt, dy, x, None, False, M, C, mean, invstd, ceff, deff, act, alpha, dC, dD, dalpha, dx, ctx.m_total,
+                     ctx.all_reduce, coef)
         g3ret = _grad_ret(dg3, s3) if g3r is not None else None
         b3ret = _grad_ret(db3, t3) if b3r is not None else None
         return (dx, None, None, _grad_ret(dalpha, sa) if alpha is not None else None, _grad_ret(dg1, s1), _grad_ret(db1, t1),
@@ -1499,15 +1471,10 @@ def bn_update_only(x, C, moving_mean, moving_var):
     update op runs (it is in UPDATE_OPS, model.py:665-666)."""
     if _meta(x):
         return
-    L = _lib.lib()
-    pre = getattr(x, "_vnet_stats", None)
+    pre = _epilogue_of(x, None, C)
     x = x.contiguous()
     M = x.numel() // C
-    mean = torch.empty(C, dtype=torch.float32, device=x.device)
-    invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-    nb = L.vnet_bn_ws_bytes(C)
-    ws = workspace(nb, x.device)
-    _bn_statistics(L, x, None, False, M, C, mean, invstd, moving_mean, moving_var, ws, nb, pre, None)
+    _bn_stats(bn_route("stats", M, C, x16=_is16(x), epilogue=pre is not None), x, None, False, M, C, moving_mean, moving_var, pre)
 
 
 # ---- stand-alone activation (API parity with layers2.prelu; the networks use the fused bn_act) ------------
