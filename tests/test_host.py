@@ -285,3 +285,20 @@ def test_bench_refuses_more_ranks_than_devices():
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "1"], cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 2 and "device(s) visible" in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_kernels_launch_only_through_the_launch_helper():
+    """Every kernel of libvnet_hip.so is launched by launch() in csrc/common.h, which also owns the dynamic-LDS attribute (set per
+    kernel and device, thread-safe).  A launch or attribute call anywhere else would bypass that: fail on any."""
+    csrc = os.path.join(ROOT, "vnet_tensorflow_amd", "csrc")
+    sources = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".inc", ".cpp"))]
+    assert "common.h" in sources and "elementwise.hip" in sources
+    offenders = []
+    for name in sources:
+        text = open(os.path.join(csrc, name)).read()
+        for word in ("hipLaunchKernel", "hipFuncSetAttribute", "<<<"):
+            if word in text and name != "common.h":
+                offenders.append((name, word))
+    assert not offenders, offenders
+    helper = open(os.path.join(csrc, "common.h")).read()
+    assert helper.count("hipLaunchKernelGGL") == 1 and helper.count("hipFuncSetAttribute") == 1

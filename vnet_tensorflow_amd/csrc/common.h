@@ -3,6 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <atomic>
+#include <mutex>
+#include <type_traits>
+#include <utility>
 #include "../../include/vnet_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -15,11 +19,58 @@ __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
     return r;
 }
 
-#define VNET_LAUNCH_CHECK()                                  \
-    do {                                                     \
-        hipError_t e__ = hipGetLastError();                  \
-        if (e__ != hipSuccess) return (int)e__;              \
-    } while (0)
+// ---- the one launch path of the library ----
+// Dynamic-LDS bytes configured for kernel K, per device (the attribute is per (kernel, device)).
+template <auto K>
+inline std::atomic<size_t> vnet_lds_set[64];
+
+// Launches K<<<grid, block, lds, st>>>(args...) and returns 0 or the hipError_t (as an int).  A non-zero `lds` first raises
+// K's dynamic-LDS limit on the current device when it is below `lds`: once per (kernel, device), again only for a larger
+// size.  Launches may come from several host threads (vnet_infer's workers, torch's autograd thread): the check that finds
+// the limit already set is one atomic load; the rare setting is serialised.
+template <auto K, typename... A>
+int launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, A&&... args) {
+    if (lds) {
+        int dev = 0;
+        if (hipError_t e = hipGetDevice(&dev)) return (int)e;
+        std::atomic<size_t>& set = vnet_lds_set<K>[dev & 63];
+        if (set.load(std::memory_order_acquire) < lds) {
+            static std::mutex mu;
+            std::lock_guard<std::mutex> lk(mu);
+            if (set.load(std::memory_order_relaxed) < lds) {
+                if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+                    return (int)e;
+                set.store(lds, std::memory_order_release);
+            }
+        }
+    }
+    hipLaunchKernelGGL(K, grid, block, lds, st, std::forward<A>(args)...);
+    return (int)hipGetLastError();
+}
+
+// Runtime value -> template argument: f(std::integral_constant<bool, b>{}) ...
+template <typename F>
+decltype(auto) with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// ... and f(std::integral_constant<int, V>{}) for the V of Vs equal to v; VNET_E_UNSUPPORTED when none is.
+template <int... Vs, typename F>
+int with_int(int v, F&& f) {
+    int r = VNET_E_UNSUPPORTED;
+    (void)((v == Vs && ((r = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return r;
+}
+
+// compute units of the current device (cached per device; 256 on MI355X)
+inline int device_cus() {
+    static std::atomic<int> cached[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    int c = cached[dev & 63].load(std::memory_order_relaxed);
+    if (c == 0) {
+        if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 8) c = 256;
+        cached[dev & 63].store(c, std::memory_order_relaxed);
+    }
+    return c;
+}
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }

@@ -441,20 +441,6 @@ __global__ void __launch_bounds__(C2_THREADS) conv2_up_f32_kernel(C2ArgsF a) {
     }
 }
 
-template <typename K>
-int c2_launch_f(K kernel, const C2ArgsF& a, int grid, size_t lds, hipStream_t st, unsigned long long& done_mask) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(__atomic_load_n(&done_mask, __ATOMIC_ACQUIRE) & bit)) {        // the level-2 filter image (64 KB) + statistics scratch exceeds the default dynamic-LDS limit
-        const int e = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e) return e;
-        __atomic_fetch_or(&done_mask, bit, __ATOMIC_RELEASE);
-    }
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(C2_THREADS), lds, st, a);
-    return (int)hipGetLastError();
-}
-
 // exactly the instantiated pairs (levels 1 and 2 of the V-Net: Cc = 2 Cf); other widths take the generic kernels
 inline bool c2_widths_ok(int Cf, int Cc) { return (Cf == 16 && Cc == 32) || (Cf == 32 && Cc == 64); }
 
@@ -464,12 +450,6 @@ inline int c2_grid(int nseg) {
     if (wg > 2048) wg = 2048;
     if (wg < 1) wg = 1;
     return wg;
-}
-
-template <typename K>
-int c2_launch(K kernel, const C2Args& a, int grid, size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(C2_THREADS), lds, st, a);
-    return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -500,18 +480,14 @@ int vnet_conv2_direct_b16(int down, const void* in, void* out, const float* w, c
     a.segx = (Wc + 15) / 16; a.nseg = B * Dc * Hc * a.segx; a.accum = accum ? 1 : 0;
     const int grid = c2_grid(a.nseg);
     const size_t wbytes = (size_t)8 * Cf * Cc * 2;
-    int e;
+    // (c2_widths_ok: Cc = 2 Cf)
     if (down) {
         const size_t lds = wbytes + (stats ? (size_t)4 * 2 * Cc * sizeof(float) : 0);
-        if (Cf == 16 && Cc == 32) e = stats ? c2_launch(conv2_down_b16_kernel<16, 32, true>, a, grid, lds, st) : c2_launch(conv2_down_b16_kernel<16, 32, false>, a, grid, lds, st);
-        else if (Cf == 32 && Cc == 64) e = stats ? c2_launch(conv2_down_b16_kernel<32, 64, true>, a, grid, lds, st) : c2_launch(conv2_down_b16_kernel<32, 64, false>, a, grid, lds, st);
-        else return VNET_E_UNSUPPORTED;
-    } else {
-        if (Cf == 16 && Cc == 32) e = c2_launch(conv2_up_b16_kernel<16, 32>, a, grid, wbytes, st);
-        else if (Cf == 32 && Cc == 64) e = c2_launch(conv2_up_b16_kernel<32, 64>, a, grid, wbytes, st);
-        else return VNET_E_UNSUPPORTED;
+        return with_int<16, 32>(Cf, [&](auto CF) {
+            return with_bool(stats, [&](auto S) { return launch<conv2_down_b16_kernel<CF, 2 * CF, S>>(dim3(grid), dim3(C2_THREADS), lds, st, a); });
+        });
     }
-    return e;
+    return with_int<16, 32>(Cf, [&](auto CF) { return launch<conv2_up_b16_kernel<CF, 2 * CF>>(dim3(grid), dim3(C2_THREADS), wbytes, st, a); });
 }
 
 // fp32 tensors (the reference's arithmetic); arguments as vnet_conv2_direct_b16, float pointers
@@ -528,16 +504,14 @@ int vnet_conv2_direct_f32(int down, const float* in, float* out, const float* w,
     a.segx = (Wc + 15) / 16; a.nseg = B * Dc * Hc * a.segx; a.accum = accum ? 1 : 0;
     const int grid = c2_grid(a.nseg);
     const size_t wbytes = (size_t)8 * Cf * Cc * 4;
-    const size_t lds = wbytes + (size_t)4 * 2 * Cc * sizeof(float);
-    static unsigned long long m0 = 0, m1 = 0, m2 = 0, m3 = 0, m4 = 0, m5 = 0;
+    const size_t lds = wbytes + (size_t)4 * 2 * Cc * sizeof(float);     // (level 2: above the default dynamic-LDS limit)
+    // (c2_widths_ok: Cc = 2 Cf)
     if (down) {
-        if (Cf == 16 && Cc == 32) return stats ? c2_launch_f(conv2_down_f32_kernel<16, 32, true>, a, grid, lds, st, m0) : c2_launch_f(conv2_down_f32_kernel<16, 32, false>, a, grid, lds, st, m1);
-        if (Cf == 32 && Cc == 64) return stats ? c2_launch_f(conv2_down_f32_kernel<32, 64, true>, a, grid, lds, st, m2) : c2_launch_f(conv2_down_f32_kernel<32, 64, false>, a, grid, lds, st, m3);
-        return VNET_E_UNSUPPORTED;
+        return with_int<16, 32>(Cf, [&](auto CF) {
+            return with_bool(stats, [&](auto S) { return launch<conv2_down_f32_kernel<CF, 2 * CF, S>>(dim3(grid), dim3(C2_THREADS), lds, st, a); });
+        });
     }
-    if (Cf == 16 && Cc == 32) return c2_launch_f(conv2_up_f32_kernel<16, 32>, a, grid, lds, st, m4);
-    if (Cf == 32 && Cc == 64) return c2_launch_f(conv2_up_f32_kernel<32, 64>, a, grid, lds, st, m5);
-    return VNET_E_UNSUPPORTED;
+    return with_int<16, 32>(Cf, [&](auto CF) { return launch<conv2_up_f32_kernel<CF, 2 * CF>>(dim3(grid), dim3(C2_THREADS), lds, st, a); });
 }
 
 }  // extern "C"

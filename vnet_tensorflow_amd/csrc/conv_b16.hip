@@ -133,10 +133,10 @@ static int conv_fwd_b16_impl(const void* x0, int C0, const void* x1, int C1, con
     if (nslab > 1) {
         const size_t total = nvox * a.Cout;
         const int blocks = (int)min((size_t)2048, (total + 255) / 256);
-        hipLaunchKernelGGL(splitk_reduce_b16_kernel, dim3(blocks), dim3(256), 0, st, a.part, a.part_stride, nslab, bias,
-                           reinterpret_cast<unsigned short*>(y0), reinterpret_cast<unsigned short*>(y1), Cy0, Cy1, a.CoutP, nvox, a.accum,
-                           reinterpret_cast<const unsigned short*>(res16), a.stats, reinterpret_cast<const unsigned short*>(a.accsrc));
-        VNET_LAUNCH_CHECK();
+        return launch<splitk_reduce_b16_kernel>(dim3(blocks), dim3(256), 0, st, a.part, a.part_stride, nslab, bias,
+                                                reinterpret_cast<unsigned short*>(y0), reinterpret_cast<unsigned short*>(y1), Cy0, Cy1,
+                                                a.CoutP, nvox, a.accum, reinterpret_cast<const unsigned short*>(res16), a.stats,
+                                                reinterpret_cast<const unsigned short*>(a.accsrc));
     }
     return VNET_OK;
 }
@@ -169,9 +169,7 @@ int vnet_conv_wgrad_b16(const void* x0, int C0, const void* x1, int C1, const vo
             } else a.part = dw;
             a.nsplit = ns;
             if (int e = launch_wgrad_zs(a, st)) return e;
-            if (a.part != dw) launch_wgrad_reduce(a.part, ns, 125, a.CinP, a.CoutP, Cin_dw, Cout, dw, st);
-            VNET_LAUNCH_CHECK();
-            return VNET_OK;
+            return a.part != dw ? launch_wgrad_reduce(a.part, ns, 125, a.CinP, a.CoutP, Cin_dw, Cout, dw, st) : VNET_OK;
         }
     }
     WgradPlan p = plan_wgrad(5, 5, 1, a.Cin, Cout, B, D, H, W, true);
@@ -197,9 +195,7 @@ int vnet_conv_wgrad_b16(const void* x0, int C0, const void* x1, int C1, const vo
         e = in4 ? launch_wgrad_bf16_rr<4, true>(a, rr_nsplit, a.ncob, st) : launch_wgrad_bf16_rr<4>(a, rr_nsplit, a.ncob, st);
         if (e) return e;
         if (direct) return VNET_OK;
-        launch_wgrad_reduce(a.part, rr_nsplit, 125, a.CinP, a.CoutP, Cin_dw, Cout, dw, st);
-        VNET_LAUNCH_CHECK();
-        return VNET_OK;
+        return launch_wgrad_reduce(a.part, rr_nsplit, 125, a.CinP, a.CoutP, Cin_dw, Cout, dw, st);
     }
     if (p.small) {
         e = p.ns == 2 ? launch_wgrad_bf16<4, 8, 8, 2, 8>(a, p.nsplit, p.ncob, p.ntg, st)
@@ -211,9 +207,7 @@ int vnet_conv_wgrad_b16(const void* x0, int C0, const void* x1, int C1, const vo
     if (e) return e;
     if (direct) return VNET_OK;
     // (Cin_dw < C0 + C1: the leading input channels only -- a network input that was zero-padded to the 16-byte unit)
-    launch_wgrad_reduce(a.part, p.nsplit, 125, a.CinP, a.CoutP, Cin_dw, Cout, dw, st);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch_wgrad_reduce(a.part, p.nsplit, 125, a.CinP, a.CoutP, Cin_dw, Cout, dw, st);
 }
 
 }  // extern "C"
@@ -274,8 +268,8 @@ struct GroupItem { WgradArgs a; int fam, nblock, nbrick, Cin_dw, T3; double unit
 
 // the plan and the launch shared by the grouped entry points: workgroups per layer by work share, longest first, slabs / direct
 // writes, the reduces of the slabs (queued when vnet_wgrad_defer is on)
-template <typename K>
-int launch_wgrad_group(std::vector<GroupItem>& items, double rounds, K k, size_t lds, unsigned long long& attr_done, void* stream) {
+template <auto K>
+int launch_wgrad_group(std::vector<GroupItem>& items, double rounds, size_t lds, void* stream) {
     if (items.empty()) return VNET_OK;
     hipStream_t st = (hipStream_t)stream;
     // work shares: a workgroup should carry total / (CUs x rounds); a layer block of `nbrick` bricks is split accordingly
@@ -304,7 +298,6 @@ int launch_wgrad_group(std::vector<GroupItem>& items, double rounds, K k, size_t
                     it.fam, it.a.Wi, it.a.Di, it.a.Cin, it.a.Cout, it.nblock, it.nbrick, it.unit, it.a.nsplit, it.nblock * it.a.nsplit,
                     it.unit * ceil_div(it.nbrick, it.a.nsplit));
     }
-    if (int ae = ensure_lds(k, lds, attr_done)) return ae;
     for (size_t i0 = 0; i0 < items.size(); i0 += WG_MAXJ) {
         WgradGroup g{};
         g.n = (int)min((size_t)WG_MAXJ, items.size() - i0);
@@ -318,12 +311,11 @@ int launch_wgrad_group(std::vector<GroupItem>& items, double rounds, K k, size_t
             blk += (unsigned)(it.nblock * it.a.nsplit);
         }
         g.blk0[g.n] = blk;
-        hipLaunchKernelGGL(k, dim3(blk), dim3(512), lds, st, g);
-        VNET_LAUNCH_CHECK();
+        if (int e = launch<K>(dim3(blk), dim3(512), lds, st, g)) return e;
     }
     for (const GroupItem& it : items)
-        if (it.a.part != it.dw) launch_wgrad_reduce(it.a.part, it.a.nsplit, it.T3, it.a.CinP, it.a.CoutP, it.Cin_dw, it.a.Cout, it.dw, st);
-    VNET_LAUNCH_CHECK();
+        if (it.a.part != it.dw)
+            if (int e = launch_wgrad_reduce(it.a.part, it.a.nsplit, it.T3, it.a.CinP, it.a.CoutP, it.Cin_dw, it.a.Cout, it.dw, st)) return e;
     return VNET_OK;
 }
 
@@ -414,9 +406,8 @@ int vnet_conv_wgrad_b16_group(const vnet_wgrad_job* jobs, int n, void* stream) {
         it.fam = fam; it.nbrick = a.nbrick; it.Cin_dw = J.Cin_dw; it.T3 = 125; it.dw = J.dw; it.ws = J.ws; it.ws_bytes = J.ws_bytes;
         items.push_back(it);
     }
-    static unsigned long long attr_done = 0;
     constexpr size_t LDS_RR = (size_t)8 * 12 * 36 * 32 + (size_t)4 * 8 * 32 * 32;
-    return launch_wgrad_group(items, rounds, wgrad5_b16_group_kernel, LDS_RR, attr_done, stream);
+    return launch_wgrad_group<wgrad5_b16_group_kernel>(items, rounds, LDS_RR, stream);
 }
 
 // 2^3 stride-2 convolution (up = 0: [B,Di,Hi,Wi,Cin] -> [B,Do,Ho,Wo,Cout]) or 2^3 transposed convolution (up = 1) on bf16
@@ -465,10 +456,9 @@ int vnet_conv2_fwd_b16(int up, const void* x, int Cin, const float* wp, const fl
     if (nslab > 1) {
         const size_t total = nvox * a.Cout;
         const int blocks = (int)min((size_t)2048, (total + 255) / 256);
-        hipLaunchKernelGGL(splitk_reduce_b16_kernel, dim3(blocks), dim3(256), 0, st, a.part, a.part_stride, nslab, bias,
-                           reinterpret_cast<unsigned short*>(y), (unsigned short*)nullptr, Cout, 0, a.CoutP, nvox, a.accum,
-                           (const unsigned short*)nullptr, a.stats, (const unsigned short*)nullptr);
-        VNET_LAUNCH_CHECK();
+        return launch<splitk_reduce_b16_kernel>(dim3(blocks), dim3(256), 0, st, a.part, a.part_stride, nslab, bias,
+                                                reinterpret_cast<unsigned short*>(y), (unsigned short*)nullptr, Cout, 0, a.CoutP, nvox,
+                                                a.accum, (const unsigned short*)nullptr, a.stats, (const unsigned short*)nullptr);
     }
     return VNET_OK;
 }
@@ -504,9 +494,7 @@ int vnet_conv2_wgrad_b16(const void* x, int Cin, const void* dy, int Cout, float
     }
     if (e) return e;
     if (direct) return VNET_OK;
-    launch_wgrad_reduce(a.part, p.nsplit, 8, a.CinP, a.CoutP, Cin, Cout, dw, st);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch_wgrad_reduce(a.part, p.nsplit, 8, a.CinP, a.CoutP, Cin, Cout, dw, st);
 }
 
 }  // extern "C"

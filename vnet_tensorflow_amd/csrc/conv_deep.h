@@ -489,18 +489,7 @@ int launch_conv_deep(const ConvArgs& a, const DeepPlan& p, hipStream_t st) {
     constexpr size_t main_bytes = 4 * (G::TILE_BYTES + 32);          // four padded tiles (> the 128 KB of a reduction round)
     const size_t lds = main_bytes + 64 * 16;
     dim3 grid(a.B * p.nbz * p.nby * p.nbx, p.ncob, p.nsplit);
-    if (a.stats && p.nsplit == 1) {
-        auto k = conv5_bf16_deep_kernel<true>;
-        static unsigned long long attr_done = 0;
-        if (int ae = ensure_lds(k, lds, attr_done)) return ae;
-        hipLaunchKernelGGL(k, grid, dim3(512), lds, st, a);
-    } else {
-        auto k = conv5_bf16_deep_kernel<false>;
-        static unsigned long long attr_done = 0;
-        if (int ae = ensure_lds(k, lds, attr_done)) return ae;
-        hipLaunchKernelGGL(k, grid, dim3(512), lds, st, a);
-    }
-    return (int)hipGetLastError();
+    return with_bool(a.stats && p.nsplit == 1, [&](auto S) { return launch<conv5_bf16_deep_kernel<S>>(grid, dim3(512), lds, st, a); });
 }
 
 }  // namespace

@@ -749,7 +749,7 @@ __global__ void __launch_bounds__(256) wgrad_reduce_batched_kernel(ReduceBatch b
 }
 
 
-void launch_wgrad_reduce(const float* part, int nsplit, int T3, int CinP, int CoutP, int Cin, int Cout, float* dw, hipStream_t st) {
+int launch_wgrad_reduce(const float* part, int nsplit, int T3, int CinP, int CoutP, int Cin, int Cout, float* dw, hipStream_t st) {
     const bool vec = (Cout % 4 == 0) && (CoutP % 4 == 0) && ((reinterpret_cast<uintptr_t>(dw) | reinterpret_cast<uintptr_t>(part)) & 15) == 0;
     {
         DeferState& ds = defer_state();
@@ -757,13 +757,14 @@ void launch_wgrad_reduce(const float* part, int nsplit, int T3, int CinP, int Co
         auto it = ds.q.find(st);
         if (it != ds.q.end() && it->second.on) {
             it->second.pending.push_back(ReduceJob{part, dw, nsplit, T3, CinP, CoutP, Cin, Cout, vec ? 1 : 0, 0u});
-            return;
+            return 0;
         }
     }
     const size_t total = (size_t)T3 * Cin * Cout / (vec ? 4 : 1);
     const int blocks = (int)min((size_t)4096, (total + 63) / 64);
-    if (vec) hipLaunchKernelGGL(wgrad_reduce_kernel<true>, dim3(blocks), dim3(256), 0, st, part, nsplit, T3, CinP, CoutP, Cin, Cout, dw);
-    else hipLaunchKernelGGL(wgrad_reduce_kernel<false>, dim3(blocks), dim3(256), 0, st, part, nsplit, T3, CinP, CoutP, Cin, Cout, dw);
+    return with_bool(vec, [&](auto V) {
+        return launch<wgrad_reduce_kernel<V>>(dim3(blocks), dim3(256), 0, st, part, nsplit, T3, CinP, CoutP, Cin, Cout, dw);
+    });
 }
 
 
@@ -1087,39 +1088,6 @@ void packed_dims(int mode, int T, int I, int O, int* Tp, int* CQ, int* NP) {
     else { *Tp = 1; *CQ = round_up(I, 16) / 4; *NP = round_up(8 * O, 16); }
 }
 
-template <typename K>
-int set_lds(K kernel, size_t bytes) {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-// The dynamic-LDS attribute is per (kernel, device): remember per device which ones are configured (a process that
-// drives a non-zero device, or several, must configure each of them once).
-template <typename K>
-int ensure_lds(K kernel, size_t bytes, unsigned long long& done_mask) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-    const unsigned long long bit = 1ull << (dev & 63);
-    // (atomic: launches may come from several host threads -- vnet_infer's workers, torch's autograd thread; setting the
-    // attribute twice is harmless, losing another device's bit to a torn read-modify-write would only repeat it)
-    if (__atomic_load_n(&done_mask, __ATOMIC_ACQUIRE) & bit) return 0;
-    const int e = set_lds(kernel, bytes);
-    if (e == 0) __atomic_fetch_or(&done_mask, bit, __ATOMIC_RELEASE);
-    return e;
-}
-
-// compute units of the current device (cached per device; 256 on MI355X)
-inline int device_cus() {
-    static int cached[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    int& c = cached[dev & 63];
-    if (c == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-        c = n;
-    }
-    return c;
-}
-
 int pick_ns(int CoutP) { return (CoutP % 64 == 0) ? 4 : (CoutP % 32 == 0) ? 2 : 1; }
 
 struct ConvPlan { int ns, ncob, nbz, nby, nbx, nsplit, cps, small, nz, half, tiny; };
@@ -1190,18 +1158,9 @@ int launch_conv_ns(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
     using G = TileGeom<KS, STRIDE, TZ, TY, TX, KX>;
     const size_t lds = (size_t)G::LDS_FLOATS * 4;
     dim3 grid(a.B * p.nbz * p.nby * p.nbx, p.ncob, p.nsplit * p.nz), block(WAVES * 64);
-    int e = 0;
-#define VNET_GO(NSV)                                                                              \
-    {                                                                                             \
-        auto k = conv_kernel<KS, STRIDE, TZ, TY, TX, WAVES, MS, NSV, UP, KX, STATS, IO16>;            \
-        static unsigned long long attr_done = 0;                                                  \
-        if (int ae = ensure_lds(k, lds, attr_done)) return ae;                                    \
-        hipLaunchKernelGGL(k, grid, block, lds, st, a);                                           \
-    }
-    if (p.ns == 4) VNET_GO(4) else if (p.ns == 2) VNET_GO(2) else VNET_GO(1)
-#undef VNET_GO
-    e = (int)hipGetLastError();
-    return e;
+    return with_int<4, 2, 1>(p.ns, [&](auto NS) {
+        return launch<conv_kernel<KS, STRIDE, TZ, TY, TX, WAVES, MS, NS, UP, KX, STATS, IO16>>(grid, block, lds, st, a);
+    });
 }
 
 
@@ -2496,24 +2455,14 @@ template <int TZ, bool IN4 = false>
 int launch_wgrad_bf16_rr(const WgradArgs& a, int nsplit, int ncob, hipStream_t st) {
     constexpr int IZ = TZ + 4, IY = 12, IX = 36;
     const size_t lds = (size_t)IZ * IY * IX * 32 + (size_t)TZ * 8 * 32 * 32;
-    auto k = wgrad5_bf16_rr_kernel<TZ, IN4>;
-    static unsigned long long attr_done = 0;
-    if (int ae = ensure_lds(k, lds, attr_done)) return ae;
-    dim3 grid(nsplit, (a.CinP / 16) * ncob, 1);
-    hipLaunchKernelGGL(k, grid, dim3(512), lds, st, a);
-    return (int)hipGetLastError();
+    return launch<wgrad5_bf16_rr_kernel<TZ, IN4>>(dim3(nsplit, (a.CinP / 16) * ncob, 1), dim3(512), lds, st, a);
 }
 
 template <int TZ, int TY, int TX, int NS, int TW>
 int launch_wgrad_bf16(const WgradArgs& a, int nsplit, int ncob, int ntg, hipStream_t st) {
     using G = TileGeom<5, 1, TZ, TY, TX, 5>;
     const size_t lds = (size_t)G::NVOX_IN * 32 + (size_t)NS * TZ * TY * (TX + 4) * 32;
-    auto k = wgrad5_bf16_kernel<TZ, TY, TX, NS, TW>;
-    static unsigned long long attr_done = 0;
-    if (int ae = ensure_lds(k, lds, attr_done)) return ae;
-    dim3 grid(nsplit, (a.CinP / 16) * ncob, ntg);
-    hipLaunchKernelGGL(k, grid, dim3(512), lds, st, a);
-    return (int)hipGetLastError();
+    return launch<wgrad5_bf16_kernel<TZ, TY, TX, NS, TW>>(dim3(nsplit, (a.CinP / 16) * ncob, ntg), dim3(512), lds, st, a);
 }
 
 struct Bf16Plan { int nsb, ncobg, nbz, nby, nbx, nsplit, cps, small, nz, half; };
@@ -2588,17 +2537,10 @@ template <int TZ, int TY, int TX, int WAVES, bool STATS = false>
 int launch_conv_bf16(const ConvArgs& a, const Bf16Plan& p, hipStream_t st) {
     using G = Bf16Geom<TZ, TY, TX>;
     dim3 grid(a.B * p.nbz * p.nby * p.nbx, p.ncobg, p.nsplit * p.nz), block(WAVES * 64);
-#define VNET_GO(NSBV)                                                                             \
-    {                                                                                             \
-        auto k = conv5_bf16_kernel<TZ, TY, TX, NSBV, WAVES, STATS>;                       \
-        const size_t lds = (size_t)G::TILE_BYTES + (size_t)25 * NSBV * 1024 + 16 + 64 * 16;       \
-        static unsigned long long attr_done = 0;                                                  \
-        if (int ae = ensure_lds(k, lds, attr_done)) return ae;                                    \
-        hipLaunchKernelGGL(k, grid, block, lds, st, a);                                           \
-    }
-    if (p.nsb == 2) VNET_GO(2) else VNET_GO(1)
-#undef VNET_GO
-    return (int)hipGetLastError();
+    return with_int<2, 1>(p.nsb, [&](auto NSB) {
+        const size_t lds = (size_t)G::TILE_BYTES + (size_t)25 * NSB * 1024 + 16 + 64 * 16;
+        return launch<conv5_bf16_kernel<TZ, TY, TX, NSB, WAVES, STATS>>(grid, block, lds, st, a);
+    });
 }
 
 }  // namespace
@@ -2643,12 +2585,7 @@ template <int KS, int STRIDE, int TZ, int TY, int TX, int NS, int TW, int KX = K
 int launch_wgrad(const WgradArgs& a, const WgradPlan& p, hipStream_t st) {
     using G = TileGeom<KS, STRIDE, TZ, TY, TX, KX>;
     const size_t lds = ((size_t)G::LDS_FLOATS + (size_t)TZ * TY * TX * NS * 16) * 4;
-    auto k = wgrad_kernel<KS, STRIDE, TZ, TY, TX, NS, TW, KX, IO16>;
-    static unsigned long long attr_done = 0;
-    if (int ae = ensure_lds(k, lds, attr_done)) return ae;
-    dim3 grid(p.nsplit, (a.CinP / 16) * p.ncob, p.ntg);
-    hipLaunchKernelGGL(k, grid, dim3(512), lds, st, a);
-    return (int)hipGetLastError();
+    return launch<wgrad_kernel<KS, STRIDE, TZ, TY, TX, NS, TW, KX, IO16>>(dim3(p.nsplit, (a.CinP / 16) * p.ncob, p.ntg), dim3(512), lds, st, a);
 }
 }  // namespace
 #include "conv_c16pp.h"
@@ -2662,74 +2599,25 @@ int conv_fwd_bf16_go(ConvArgs& a, const Bf16Plan& p, int nslab, int C0, int C1, 
         using GC = Bf16Geom<4, 8, 16>;
         a.nbz = ceil_div(D, 4); a.nby = ceil_div(H, 8); a.nbx = ceil_div(W, 16);
         const size_t lds = (size_t)GC::TILE_BYTES + 65 * 1024 + 64 * 16 + 8 * 32 * 4;
-        {
-            if (!a.in4 && conv_bf16_use_c16pp(a.Cin, a.Cout, C0, C1, Cy0, Cy1, B, D, H, W)) {
-                // filter out of LDS, two 4-wave workgroups per CU (conv_c16pp.h): the same 4x8x16 bricks
-                const int grid = 2 * (device_cus() / 8) * 8;
-                if (a.stats) {
-                    auto k = conv5_bf16_c16pp_kernel<true>;
-                    static unsigned long long attr_done = 0;
-                    if (int ae = ensure_lds(k, PP_LDS, attr_done)) return ae;
-                    hipLaunchKernelGGL(k, dim3(grid), dim3(256), PP_LDS, st, a);
-                } else {
-                    auto k = conv5_bf16_c16pp_kernel<false>;
-                    static unsigned long long attr_done = 0;
-                    if (int ae = ensure_lds(k, PP_LDS, attr_done)) return ae;
-                    hipLaunchKernelGGL(k, dim3(grid), dim3(256), PP_LDS, st, a);
-                }
-                VNET_LAUNCH_CHECK();
-                return -1;
-            }
-            if (a.in4) {              // the multi-modality network input: x-im2col in LDS, 2.5x fewer MFMAs
-                if (a.stats) {
-                    auto k = conv5_bf16_c16_kernel<4, 8, 16, true, true>;
-                    static unsigned long long attr_done = 0;
-                    if (int ae = ensure_lds(k, lds, attr_done)) return ae;
-                    hipLaunchKernelGGL(k, dim3(256), dim3(512), lds, st, a);
-                } else {
-                    auto k = conv5_bf16_c16_kernel<4, 8, 16, false, true>;
-                    static unsigned long long attr_done = 0;
-                    if (int ae = ensure_lds(k, lds, attr_done)) return ae;
-                    hipLaunchKernelGGL(k, dim3(256), dim3(512), lds, st, a);
-                }
-                VNET_LAUNCH_CHECK();
-                return -1;
-            }
-        }
-        if (a.stats) {
-            auto k = conv5_bf16_c16_kernel<4, 8, 16, true>;
-            static unsigned long long attr_done = 0;
-            if (int ae = ensure_lds(k, lds, attr_done)) return ae;
-            hipLaunchKernelGGL(k, dim3(256), dim3(512), lds, st, a);
+        int e;
+        if (!a.in4 && conv_bf16_use_c16pp(a.Cin, a.Cout, C0, C1, Cy0, Cy1, B, D, H, W)) {
+            // filter out of LDS, two 4-wave workgroups per CU (conv_c16pp.h): the same 4x8x16 bricks
+            const int grid = 2 * (device_cus() / 8) * 8;
+            e = with_bool(a.stats, [&](auto S) { return launch<conv5_bf16_c16pp_kernel<S>>(dim3(grid), dim3(256), PP_LDS, st, a); });
+        } else if (a.in4) {       // the multi-modality network input: x-im2col in LDS, 2.5x fewer MFMAs
+            e = with_bool(a.stats, [&](auto S) { return launch<conv5_bf16_c16_kernel<4, 8, 16, S, true>>(dim3(256), dim3(512), lds, st, a); });
         } else {
-            auto k = conv5_bf16_c16_kernel<4, 8, 16, false>;
-            static unsigned long long attr_done = 0;
-            if (int ae = ensure_lds(k, lds, attr_done)) return ae;
-            hipLaunchKernelGGL(k, dim3(256), dim3(512), lds, st, a);
+            e = with_bool(a.stats, [&](auto S) { return launch<conv5_bf16_c16_kernel<4, 8, 16, S>>(dim3(256), dim3(512), lds, st, a); });
         }
-        VNET_LAUNCH_CHECK();
-        return -1;            // done, no reduce
+        return e ? e : -1;    // done, no reduce
     }
-    {
-        if (conv_bf16_use_r32(a.Cout, Cy0, Cy1, B, D, H, W) && nslab == 1) {
-            // 32-cout blocks, many bricks, bf16 shadows: the row-pair kernel (11 B + 5 A fragments per 20 MFMAs)
-            using GR = Bf16Geom<4, 16, 16>;
-            a.nbz = ceil_div(D, 4); a.nby = ceil_div(H, 16); a.nbx = ceil_div(W, 16);
-            const size_t lds = (size_t)GR::TILE_BYTES + 2 * (25 * 1024 + 16) + 64 * 16 + 16 * 64 * 4;
-            if (a.stats) {
-                auto k = conv5_bf16_r32_kernel<true>;
-                static unsigned long long attr_done = 0;
-                if (int ae = ensure_lds(k, lds, attr_done)) return ae;
-                hipLaunchKernelGGL(k, dim3(256), dim3(512), lds, st, a);
-            } else {
-                auto k = conv5_bf16_r32_kernel<false>;
-                static unsigned long long attr_done = 0;
-                if (int ae = ensure_lds(k, lds, attr_done)) return ae;
-                hipLaunchKernelGGL(k, dim3(256), dim3(512), lds, st, a);
-            }
-            VNET_LAUNCH_CHECK();
-            return -1;
-        }
+    if (conv_bf16_use_r32(a.Cout, Cy0, Cy1, B, D, H, W) && nslab == 1) {
+        // 32-cout blocks, many bricks, bf16 shadows: the row-pair kernel (11 B + 5 A fragments per 20 MFMAs)
+        using GR = Bf16Geom<4, 16, 16>;
+        a.nbz = ceil_div(D, 4); a.nby = ceil_div(H, 16); a.nbx = ceil_div(W, 16);
+        const size_t lds = (size_t)GR::TILE_BYTES + 2 * (25 * 1024 + 16) + 64 * 16 + 16 * 64 * 4;
+        const int e = with_bool(a.stats, [&](auto S) { return launch<conv5_bf16_r32_kernel<S>>(dim3(256), dim3(512), lds, st, a); });
+        return e ? e : -1;
     }
     return (a.stats && nslab == 1)
          ? (p.small ? launch_conv_bf16<8, 8, 8, 8, true>(a, p, st)

@@ -90,19 +90,15 @@ int vnet_pack_weights(int mode, const float* w, float* wp, int taps, int I, int 
         if (taps != 125) return VNET_E_UNSUPPORTED;
         int nchunk, ncob; x3_packed_dims(mode == VNET_PACK_BWD_X3, I, O, &nchunk, &ncob);
         const uint32_t units = (uint32_t)nchunk * X3_NPAIR * ncob * 64;
-        hipLaunchKernelGGL(x3_pack_kernel, dim3(min(4096u, (units + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           mode == VNET_PACK_BWD_X3 ? 1 : 0, w, reinterpret_cast<u32x4*>(wp), I, O, ncob, units);
-        VNET_LAUNCH_CHECK();
-        return VNET_OK;
+        return launch<x3_pack_kernel>(dim3(min(4096u, (units + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                                      mode == VNET_PACK_BWD_X3 ? 1 : 0, w, reinterpret_cast<u32x4*>(wp), I, O, ncob, units);
     }
     if (mode == VNET_PACK_FWD_BF16 || mode == VNET_PACK_BWD_BF16) {
         int nchunk, ncob; packed_dims_bf16(mode, I, O, &nchunk, &ncob);
         const size_t total = (size_t)nchunk * taps * ncob * 512;
         const int blocks = (int)min((size_t)4096, (total + 255) / 256);
-        hipLaunchKernelGGL(pack_bf16_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, mode, w,
-                           reinterpret_cast<unsigned short*>(wp), taps, I, O, ncob, total);
-        VNET_LAUNCH_CHECK();
-        return VNET_OK;
+        return launch<pack_bf16_kernel>(dim3(blocks), dim3(256), 0, (hipStream_t)stream, mode, w,
+                                        reinterpret_cast<unsigned short*>(wp), taps, I, O, ncob, total);
     }
     const int base = mode & ~VNET_PACK_ROUND_BF16;
     if (base < 0 || base > 2) return VNET_E_UNSUPPORTED;
@@ -110,9 +106,7 @@ int vnet_pack_weights(int mode, const float* w, float* wp, int taps, int I, int 
     int Tp, CQ, NP; packed_dims(base, taps, I, O, &Tp, &CQ, &NP);
     const size_t total = (size_t)Tp * CQ * NP * 4;
     const int blocks = (int)min((size_t)4096, (total + 255) / 256);
-    hipLaunchKernelGGL(pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, mode, w, wp, taps, I, O, CQ, NP, total);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<pack_kernel>(dim3(blocks), dim3(256), 0, (hipStream_t)stream, mode, w, wp, taps, I, O, CQ, NP, total);
 }
 
 int vnet_packed_dims(int mode, int taps, int I, int O, int* CQ, int* NP) {
@@ -127,9 +121,7 @@ int vnet_packed_dims(int mode, int taps, int I, int O, int* CQ, int* NP) {
 
 int vnet_pack_weights_batched(const void* descs_dev, int n, void* stream) {
     if (!descs_dev || n <= 0) return VNET_E_BADARG;
-    hipLaunchKernelGGL(pack_batched_kernel, dim3(512, n), dim3(256), 0, (hipStream_t)stream, (const long long*)descs_dev);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<pack_batched_kernel>(dim3(512, n), dim3(256), 0, (hipStream_t)stream, (const long long*)descs_dev);
 }
 
 size_t vnet_conv_ws_bytes(int ks, int kx, int stride, int up, int Cin, int Cout, int B, int Do, int Ho, int Wo) {
@@ -228,9 +220,8 @@ static int conv_fwd_impl(int ks, int kx, int stride, int up, const float* x0, in
     if (nslab > 1) {
         const size_t total = nvox * a.Cout;
         const int blocks = (int)min((size_t)2048, (total + 255) / 256);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, a.part, a.part_stride, nslab, bias,
-                           y0, y1, Cy0, Cy1, a.CoutP, nvox, a.accum, a.res, a.stats);
-        VNET_LAUNCH_CHECK();
+        return launch<splitk_reduce_kernel>(dim3(blocks), dim3(256), 0, st, a.part, a.part_stride, nslab, bias,
+                                            y0, y1, Cy0, Cy1, a.CoutP, nvox, a.accum, a.res, a.stats, nullptr);
     }
     return VNET_OK;
 }
@@ -300,8 +291,7 @@ int vnet_wgrad_flush(void* stream) {
             const size_t total = (size_t)b.job[k].T3 * b.job[k].Cin * b.job[k].Cout / (b.job[k].vec ? 4 : 1);
             blk += (unsigned)min((size_t)1024, (total + 63) / 64);
         }
-        hipLaunchKernelGGL(wgrad_reduce_batched_kernel, dim3(blk), dim3(256), 0, st, b);
-        VNET_LAUNCH_CHECK();
+        if (int e = launch<wgrad_reduce_batched_kernel>(dim3(blk), dim3(256), 0, st, b)) return e;
     }
     return VNET_OK;
 }
@@ -356,9 +346,7 @@ int vnet_conv_wgrad(int ks, int kx, int stride, const float* x0, int C0, const f
     }
     if (e) return e;
     if (direct) return VNET_OK;
-    launch_wgrad_reduce(a.part, p.nsplit, T3, a.CinP, a.CoutP, a.Cin, Cout, dw, st);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch_wgrad_reduce(a.part, p.nsplit, T3, a.CinP, a.CoutP, a.Cin, Cout, dw, st);
 }
 
 size_t vnet_wgrad_bf16_ws_bytes(int Cin, int Cout, int B, int D, int H, int W) {

@@ -66,25 +66,17 @@ int vnet_conv_fwd_x3(const float* x0, int C0, const float* x1, int C1, const voi
     // y0 / y1 -- each block finds its own destination: the backward-data launch of a 2C -> C layer with C = 16).  Round 6: from 2 x grid single-block items on (was 4 x): 32^3 64->64 0.149 -> 0.140 ms, 128->64 0.275 -> 0.263
     const bool w8 = W == 8;                            // the narrow brick (X3G<true>): one cout block per item
     const bool nb2 = !w8 && (a.Cout % 32 == 0) && p.items * p.nks >= 2 * (long)grid && tuning().x3_nb2 != 0;
-#define VNET_X3_GO(STATSV, NBV, W8V)                                                     \
-    {                                                                                    \
-        auto k = conv5_x3_kernel<STATSV, NBV, W8V>;                                      \
-        static unsigned long long attr_done = 0;                                         \
-        if (int ae = ensure_lds(k, X3G<W8V>::LDS, attr_done)) return ae;                 \
-        hipLaunchKernelGGL(k, dim3(grid), dim3(512), X3G<W8V>::LDS, st, a);              \
-    }
-    if (stats && p.nks == 1) { if (w8) VNET_X3_GO(true, 1, true) else if (nb2) VNET_X3_GO(true, 2, false) else VNET_X3_GO(true, 1, false) }
-    else { if (w8) VNET_X3_GO(false, 1, true) else if (nb2) VNET_X3_GO(false, 2, false) else VNET_X3_GO(false, 1, false) }
-#undef VNET_X3_GO
-    VNET_LAUNCH_CHECK();
-    if (p.nks > 1) {
-        const size_t total = nvox * a.Cout;
-        const int blocks = (int)min((size_t)2048, (total + 255) / 256);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, a.part, a.part_stride, p.nks, bias,
-                           y0, y1, Cy0, Cy1, a.CoutP, nvox, a.accum, a.res, a.stats, a.accsrc);
-        VNET_LAUNCH_CHECK();
-    }
-    return VNET_OK;
+    const int e = with_bool(stats && p.nks == 1, [&](auto S) {
+        return w8 ? launch<conv5_x3_kernel<S, 1, true>>(dim3(grid), dim3(512), X3G<true>::LDS, st, a)
+                  : with_int<2, 1>(nb2 ? 2 : 1, [&](auto NB) {
+                        return launch<conv5_x3_kernel<S, NB, false>>(dim3(grid), dim3(512), X3G<false>::LDS, st, a);
+                    });
+    });
+    if (e || p.nks <= 1) return e;
+    const size_t total = nvox * a.Cout;
+    const int blocks = (int)min((size_t)2048, (total + 255) / 256);
+    return launch<splitk_reduce_kernel>(dim3(blocks), dim3(256), 0, st, a.part, a.part_stride, p.nks, bias,
+                                        y0, y1, Cy0, Cy1, a.CoutP, nvox, a.accum, a.res, a.stats, a.accsrc);
 }
 
 int vnet_wgrad_x3_ok(int C0, int C1, int Cout, int B, int D, int H, int W) {
@@ -114,22 +106,10 @@ int vnet_conv_wgrad_x3(const float* x0, int C0, const float* x1, int C1, const f
     const bool direct = p.nsplit == 1;                 // one slab: the slab IS dw (TF layout [tap][Cin][Cout])
     if (!direct && (!ws || ws_bytes < need)) return VNET_E_WORKSPACE;
     a.part = direct ? dw : reinterpret_cast<float*>(ws);
-    if (W == 8) {                                      // the narrow brick (XWG<true>)
-        auto k = wgrad5_x3_kernel<true>;
-        static unsigned long long attr_done = 0;
-        if (int ae = ensure_lds(k, XWG<true>::LDS, attr_done)) return ae;
-        hipLaunchKernelGGL(k, dim3(p.nsplit, p.nblk), dim3(512), XWG<true>::LDS, st, a);
-    } else {
-        auto k = wgrad5_x3_kernel<false>;
-        static unsigned long long attr_done = 0;
-        if (int ae = ensure_lds(k, XW_LDS, attr_done)) return ae;
-        hipLaunchKernelGGL(k, dim3(p.nsplit, p.nblk), dim3(512), XW_LDS, st, a);
-    }
-    VNET_LAUNCH_CHECK();
-    if (direct) return VNET_OK;
-    launch_wgrad_reduce(a.part, p.nsplit, 125, a.CinP, a.CoutP, a.Cin, Cout, dw, st);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    // W == 8: the narrow brick (XWG<true>)
+    const int e = with_bool(W == 8, [&](auto N) { return launch<wgrad5_x3_kernel<N>>(dim3(p.nsplit, p.nblk), dim3(512), XWG<N>::LDS, st, a); });
+    if (e || direct) return e;
+    return launch_wgrad_reduce(a.part, p.nsplit, 125, a.CinP, a.CoutP, a.Cin, Cout, dw, st);
 }
 
 #ifdef VNET_STAMPS

@@ -1650,18 +1650,14 @@ __global__ void dropout_bwd_b16_kernel(const u32x4* __restrict__ dy, const uint8
 }
 }  // namespace
 
-#define K_SWITCH(K, STMT)                                                   \
-    switch (K) {                                                            \
-        case 1: { constexpr int KK = 1; STMT; } break;                      \
-        case 2: { constexpr int KK = 2; STMT; } break;                      \
-        case 3: { constexpr int KK = 3; STMT; } break;                      \
-        case 4: { constexpr int KK = 4; STMT; } break;                      \
-        case 5: { constexpr int KK = 5; STMT; } break;                      \
-        case 6: { constexpr int KK = 6; STMT; } break;                      \
-        case 7: { constexpr int KK = 7; STMT; } break;                      \
-        case 8: { constexpr int KK = 8; STMT; } break;                      \
-        default: return VNET_E_UNSUPPORTED;                                 \
-    }
+// the class count K (1..8) as a template argument
+template <typename F>
+static int with_k(int K, F&& f) { return with_int<1, 2, 3, 4, 5, 6, 7, 8>(K, f); }
+// the (BCAST, HASR) instantiations of the bf16 batch-norm kernels: broadcast statistics never come with a residual
+template <typename F>
+static int with_bcast_r(bool bcast, bool hasr, F&& f) {
+    return bcast ? f(std::true_type{}, std::false_type{}) : with_bool(hasr, [&](auto R) { return f(std::false_type{}, R); });
+}
 
 extern "C" {
 
@@ -1673,19 +1669,19 @@ size_t vnet_loss_ws_bytes(int B, int K) { return (size_t)B * EW_MAXBLK * (3 * K 
 static int bn_partial_moments(const float* x, const float* r, int bcast, int64_t M, int C, float* partial, hipStream_t st, int* nblk_out) {
     const int Cs = bcast ? 1 : C;
     const int mode = red_mode(Cs);
-    int nblk;
+    int nblk, e;
     if (mode == 0) {
         const size_t nq = (size_t)M * (Cs / 4);
         nblk = ew_blocks(nq);
-        hipLaunchKernelGGL(bn_stats_vec_kernel, dim3(nblk), dim3(EW_BLOCK), 0, st, (const float4*)x, (const float4*)r, nq, Cs / 4, partial);
+        e = launch<bn_stats_vec_kernel>(dim3(nblk), dim3(EW_BLOCK), 0, st, (const float4*)x, (const float4*)r, nq, Cs / 4, partial);
     } else if (mode == 1) {
         nblk = ew_blocks((size_t)M);
-        hipLaunchKernelGGL(bn_stats_row_kernel, dim3(nblk), dim3(EW_BLOCK), 0, st, x, r, (size_t)M, Cs, partial);
+        e = launch<bn_stats_row_kernel>(dim3(nblk), dim3(EW_BLOCK), 0, st, x, r, (size_t)M, Cs, partial);
     } else {
         nblk = ew_blocks((size_t)M * Cs);
-        hipLaunchKernelGGL(bn_stats_generic_kernel, dim3(nblk), dim3(EW_BLOCK), 0, st, x, r, (size_t)M * Cs, Cs, partial);
+        e = launch<bn_stats_generic_kernel>(dim3(nblk), dim3(EW_BLOCK), 0, st, x, r, (size_t)M * Cs, Cs, partial);
     }
-    VNET_LAUNCH_CHECK();
+    if (e) return e;
     *nblk_out = nblk;
     return VNET_OK;
 }
@@ -1701,19 +1697,15 @@ int vnet_bn_stats(const float* x, const float* r, int bcast, int64_t M, int C, f
     int nblk;
     const int rc = bn_partial_moments(x, r, bcast, M, C, partial, st, &nblk);
     if (rc != VNET_OK) return rc;
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, st, partial, nblk, bcast ? 1 : C, C, (double)M, eps, momentum,
-                       mean, invstd, moving_mean, moving_var);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<bn_finalize_kernel>(dim3(C), dim3(256), 0, st, partial, nblk, bcast ? 1 : C, C, (double)M, eps, momentum,
+                                      mean, invstd, moving_mean, moving_var);
 }
 
 int vnet_bn_finalize_partial(const float* partial, int rows, int C, double M_total, float eps, float momentum,
                              float* mean, float* invstd, float* moving_mean, float* moving_var, void* stream) {
     if (!partial || !mean || !invstd || rows <= 0 || C <= 0 || C > MAXC || M_total <= 0.0) return VNET_E_BADARG;
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, partial, rows, C, C, M_total, eps, momentum,
-                       mean, invstd, moving_mean, moving_var);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<bn_finalize_kernel>(dim3(C), dim3(256), 0, (hipStream_t)stream, partial, rows, C, C, M_total, eps, momentum,
+                                      mean, invstd, moving_mean, moving_var);
 }
 
 int vnet_bn_moments(const float* x, const float* r, int bcast, int64_t M, int C, double* sums,
@@ -1725,18 +1717,14 @@ int vnet_bn_moments(const float* x, const float* r, int bcast, int64_t M, int C,
     int nblk;
     const int rc = bn_partial_moments(x, r, bcast, M, C, (float*)ws, st, &nblk);
     if (rc != VNET_OK) return rc;
-    hipLaunchKernelGGL(bn_moments_kernel, dim3(C), dim3(256), 0, st, (const float*)ws, nblk, bcast ? 1 : C, C, sums);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<bn_moments_kernel>(dim3(C), dim3(256), 0, st, (const float*)ws, nblk, bcast ? 1 : C, C, sums);
 }
 
 int vnet_bn_finalize(const double* sums, double M_total, int C, float eps, float momentum,
                      float* mean, float* invstd, float* moving_mean, float* moving_var, void* stream) {
     if (!sums || !mean || !invstd || M_total <= 0.0 || C <= 0 || C > MAXC) return VNET_E_BADARG;
-    hipLaunchKernelGGL(bn_finalize_sums_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sums, C, M_total, eps, momentum,
-                       mean, invstd, moving_mean, moving_var);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<bn_finalize_sums_kernel>(dim3(1), dim3(256), 0, (hipStream_t)stream, sums, C, M_total, eps, momentum,
+                                           mean, invstd, moving_mean, moving_var);
 }
 
 int vnet_bn_act_fwd(const float* x, const float* r, int bcast, int64_t M, int C,
@@ -1748,10 +1736,9 @@ int vnet_bn_act_fwd(const float* x, const float* r, int bcast, int64_t M, int C,
     BnP p{}; p.x = x; p.r = r; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta; p.alpha = alpha;
     p.out = y; p.outh = nullptr; p.M = (size_t)M; p.C = C; p.bcast = bcast; p.act = act;
     hipStream_t st = (hipStream_t)stream;
-    if (C % 4 == 0) hipLaunchKernelGGL(bn_act_fwd_kernel<true>, dim3(ew_blocks((size_t)M * C / 4 / 4 + 1) ), dim3(EW_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL(bn_act_fwd_kernel<false>, dim3(ew_blocks((size_t)M * C / 4 + 1)), dim3(EW_BLOCK), 0, st, p);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return with_bool(C % 4 == 0, [&](auto V) {     // (float4 lanes)
+        return launch<bn_act_fwd_kernel<V>>(dim3(ew_blocks((size_t)M * C / 4 / (V ? 4 : 1) + 1)), dim3(EW_BLOCK), 0, st, p);
+    });
 }
 
 static int bn_bwd_fill(BnP& p, const float* dy, const float* x, const float* r, int bcast, int64_t M, int C,
@@ -1772,15 +1759,11 @@ int vnet_bn_act_bwd_reduce(const float* dy, const float* x, const float* r, int 
     BnP p{}; bn_bwd_fill(p, dy, x, r, bcast, M, C, mean, invstd, gamma, beta, act, alpha);
     p.partial = (float*)ws;
     const int mode = red_mode(C);
-    int nblk;
-    if (mode == 0) { nblk = ew_blocks((size_t)M * C / 4 / 4 + 1); hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<0>, dim3(nblk), dim3(EW_BLOCK), 0, st, p); }
-    else if (mode == 1) { nblk = ew_blocks((size_t)M); hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<1>, dim3(nblk), dim3(EW_BLOCK), 0, st, p); }
-    else { nblk = ew_blocks((size_t)M * C / 4 + 1); hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<2>, dim3(nblk), dim3(EW_BLOCK), 0, st, p); }
-    VNET_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sum_finalize_kernel<float>, dim3(C), dim3(256), 0, st, (const float*)p.partial, nblk, 3, C, dbeta, dgamma,
-                       act == VNET_ACT_PRELU ? dalpha : (float*)nullptr);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    const int nblk = mode == 0 ? ew_blocks((size_t)M * C / 4 / 4 + 1) : mode == 1 ? ew_blocks((size_t)M) : ew_blocks((size_t)M * C / 4 + 1);
+    if (int e = with_int<0, 1, 2>(mode, [&](auto MODE) { return launch<bn_act_bwd_reduce_kernel<MODE>>(dim3(nblk), dim3(EW_BLOCK), 0, st, p); }))
+        return e;
+    return launch<sum_finalize_kernel<float>>(dim3(C), dim3(256), 0, st, (const float*)p.partial, nblk, 3, C, dbeta, dgamma,
+                                              act == VNET_ACT_PRELU ? dalpha : (float*)nullptr);
 }
 
 int vnet_bn_act_bwd_apply(const float* dy, const float* x, const float* r, int bcast, int64_t M, int C,
@@ -1795,10 +1778,9 @@ int vnet_bn_act_bwd_apply(const float* dy, const float* x, const float* r, int b
     p.invM = (float)(1.0 / M_total);
     p.extra = xhat_coef;
     p.out = ds; p.outh = nullptr; p.dgamma = sum_dz_xhat; p.dbeta = sum_dz;
-    if (C % 4 == 0) hipLaunchKernelGGL(bn_act_bwd_apply_kernel<true>, dim3(ew_blocks((size_t)M * C / 4 / 4 + 1)), dim3(EW_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL(bn_act_bwd_apply_kernel<false>, dim3(ew_blocks((size_t)M * C / 4 + 1)), dim3(EW_BLOCK), 0, st, p);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return with_bool(C % 4 == 0, [&](auto V) {     // (float4 lanes)
+        return launch<bn_act_bwd_apply_kernel<V>>(dim3(ew_blocks((size_t)M * C / 4 / (V ? 4 : 1) + 1)), dim3(EW_BLOCK), 0, st, p);
+    });
 }
 
 int vnet_bn_act_bwd(const float* dy, const float* x, const float* r, int bcast, int64_t M, int C,
@@ -1821,9 +1803,7 @@ int vnet_bn_chain_coef_fwd(int kind, int C, float eps, float momentum, const flo
     ChainP p{}; p.kind = kind; p.C = C; p.eps = eps; p.momentum = momentum; p.mean = mean; p.invstd = invstd;
     p.g1 = g1; p.b1 = b1; p.g2 = g2; p.b2 = b2; p.g3 = g3; p.b3 = b3; p.ceff = ceff; p.deff = deff;
     p.mm2 = mm2; p.mv2 = mv2; p.mm3 = mm3; p.mv3 = mv3;
-    hipLaunchKernelGGL(bn_chain_fwd_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, (hipStream_t)stream, p);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<bn_chain_fwd_kernel>(dim3(ceil_div(C, 64)), dim3(64), 0, (hipStream_t)stream, p);
 }
 
 int vnet_bn_chain_coef_bwd(int kind, int C, float eps, double M_total, const float* mean, const float* invstd,
@@ -1837,9 +1817,7 @@ int vnet_bn_chain_coef_bwd(int kind, int C, float eps, double M_total, const flo
     ChainP p{}; p.kind = kind; p.C = C; p.eps = eps; p.M = M_total; p.mean = mean; p.invstd = invstd;
     p.g1 = g1; p.g2 = g2; p.g3 = g3; p.dC_local = dC_local; p.dD_local = dD_local; p.dC_global = dC_global;
     p.dg1 = dg1; p.db1 = db1; p.dg2 = dg2; p.db2 = db2; p.dg3 = dg3; p.db3 = db3; p.extra = xhat_coef;
-    hipLaunchKernelGGL(bn_chain_bwd_kernel, dim3(ceil_div(C, 64)), dim3(64), 0, (hipStream_t)stream, p);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<bn_chain_bwd_kernel>(dim3(ceil_div(C, 64)), dim3(64), 0, (hipStream_t)stream, p);
 }
 
 int vnet_act_fwd(const float* x, int64_t M, int C, int act, const float* alpha, float* y, void* stream) {
@@ -1848,10 +1826,9 @@ int vnet_act_fwd(const float* x, int64_t M, int C, int act, const float* alpha, 
     if (act < 0 || act > 3) return VNET_E_UNSUPPORTED;
     BnP p{}; p.x = x; p.alpha = alpha; p.out = y; p.M = (size_t)M; p.C = C; p.act = act; p.identity = 1;
     hipStream_t st = (hipStream_t)stream;
-    if (C % 4 == 0) hipLaunchKernelGGL(bn_act_fwd_kernel<true>, dim3(ew_blocks((size_t)M * C / 4 / 4 + 1)), dim3(EW_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL(bn_act_fwd_kernel<false>, dim3(ew_blocks((size_t)M * C / 4 + 1)), dim3(EW_BLOCK), 0, st, p);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return with_bool(C % 4 == 0, [&](auto V) {     // (float4 lanes)
+        return launch<bn_act_fwd_kernel<V>>(dim3(ew_blocks((size_t)M * C / 4 / (V ? 4 : 1) + 1)), dim3(EW_BLOCK), 0, st, p);
+    });
 }
 
 int vnet_act_bwd(const float* dy, const float* x, int64_t M, int C, int act, const float* alpha,
@@ -1863,19 +1840,17 @@ int vnet_act_bwd(const float* dy, const float* x, int64_t M, int C, int act, con
     BnP p{}; p.x = x; p.dy = dy; p.alpha = alpha; p.partial = (float*)ws; p.M = (size_t)M; p.C = C; p.act = act; p.identity = 1;
     if (act == VNET_ACT_PRELU) {
         const int mode = red_mode(C);
-        int nblk;
-        if (mode == 0) { nblk = ew_blocks((size_t)M * C / 4 / 4 + 1); hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<0>, dim3(nblk), dim3(EW_BLOCK), 0, st, p); }
-        else if (mode == 1) { nblk = ew_blocks((size_t)M); hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<1>, dim3(nblk), dim3(EW_BLOCK), 0, st, p); }
-        else { nblk = ew_blocks((size_t)M * C / 4 + 1); hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<2>, dim3(nblk), dim3(EW_BLOCK), 0, st, p); }
-        VNET_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sum_finalize_kernel<float>, dim3(C), dim3(256), 0, st, (const float*)p.partial, nblk, 3, C, (float*)nullptr, (float*)nullptr, dalpha);
-        VNET_LAUNCH_CHECK();
+        const int nblk = mode == 0 ? ew_blocks((size_t)M * C / 4 / 4 + 1) : mode == 1 ? ew_blocks((size_t)M) : ew_blocks((size_t)M * C / 4 + 1);
+        if (int e = with_int<0, 1, 2>(mode, [&](auto MODE) { return launch<bn_act_bwd_reduce_kernel<MODE>>(dim3(nblk), dim3(EW_BLOCK), 0, st, p); }))
+            return e;
+        if (int e = launch<sum_finalize_kernel<float>>(dim3(C), dim3(256), 0, st, (const float*)p.partial, nblk, 3, C, (float*)nullptr,
+                                                       (float*)nullptr, dalpha))
+            return e;
     }
     p.out = dx;
-    if (C % 4 == 0) hipLaunchKernelGGL(bn_act_bwd_apply_kernel<true>, dim3(ew_blocks((size_t)M * C / 4 / 4 + 1)), dim3(EW_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL(bn_act_bwd_apply_kernel<false>, dim3(ew_blocks((size_t)M * C / 4 + 1)), dim3(EW_BLOCK), 0, st, p);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return with_bool(C % 4 == 0, [&](auto V) {     // (float4 lanes)
+        return launch<bn_act_bwd_apply_kernel<V>>(dim3(ew_blocks((size_t)M * C / 4 / (V ? 4 : 1) + 1)), dim3(EW_BLOCK), 0, st, p);
+    });
 }
 
 int vnet_colsum(const float* x, float* out, int64_t M, int C, void* ws, size_t ws_bytes, void* stream) {
@@ -1883,19 +1858,17 @@ int vnet_colsum(const float* x, float* out, int64_t M, int C, void* ws, size_t w
     if (!ws || ws_bytes < vnet_colsum_ws_bytes(C)) return VNET_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)ws;
-    int nblk;
+    int nblk, e;
     if (red_mode(C) == 0) {
         const size_t nq = (size_t)M * (C / 4);
         nblk = ew_blocks(nq / 4 + 1);
-        hipLaunchKernelGGL(colsum_vec_kernel, dim3(nblk), dim3(EW_BLOCK), 0, st, (const float4*)x, nq, C / 4, partial);
+        e = launch<colsum_vec_kernel>(dim3(nblk), dim3(EW_BLOCK), 0, st, (const float4*)x, nq, C / 4, partial);
     } else {
         nblk = ew_blocks((size_t)M * C / 4 + 1);
-        hipLaunchKernelGGL(colsum_generic_kernel, dim3(nblk), dim3(EW_BLOCK), 0, st, x, (size_t)M * C, C, partial);
+        e = launch<colsum_generic_kernel>(dim3(nblk), dim3(EW_BLOCK), 0, st, x, (size_t)M * C, C, partial);
     }
-    VNET_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sum_finalize_kernel<float>, dim3(C), dim3(256), 0, st, (const float*)partial, nblk, 1, C, out, (float*)nullptr, (float*)nullptr);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    if (e) return e;
+    return launch<sum_finalize_kernel<float>>(dim3(C), dim3(256), 0, st, (const float*)partial, nblk, 1, C, out, (float*)nullptr, (float*)nullptr);
 }
 
 int vnet_head_fwd(const float* x, const float* w, const float* bias, float* y, int64_t M, int C, int K, void* stream) {
@@ -1903,9 +1876,7 @@ int vnet_head_fwd(const float* x, const float* w, const float* bias, float* y, i
     if (C * K > 1024) return VNET_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = ew_blocks((size_t)M / 2 + 1);
-    K_SWITCH(K, hipLaunchKernelGGL(head_fwd_kernel<KK>, dim3(nblk), dim3(EW_BLOCK), 0, st, x, w, bias, y, (size_t)M, C));
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return with_k(K, [&](auto KK) { return launch<head_fwd_kernel<KK>>(dim3(nblk), dim3(EW_BLOCK), 0, st, x, w, bias, y, (size_t)M, C); });
 }
 
 int vnet_head_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db,
@@ -1915,18 +1886,20 @@ int vnet_head_bwd(const float* x, const float* w, const float* dy, float* dx, fl
     if (!ws || ws_bytes < vnet_head_ws_bytes(C, K)) return VNET_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)ws;
-    int nblk;
+    int nblk, e;
     if ((C & 3) == 0 && is_pow2(C / 4) && C / 4 <= EW_BLOCK) {
         nblk = ew_blocks((size_t)M * (C / 4) / 4 + 1);
-        K_SWITCH(K, hipLaunchKernelGGL(head_bwd_kernel<KK>, dim3(nblk), dim3(EW_BLOCK), 0, st, x, w, dy, dx, (size_t)M, C, partial));
+        e = with_k(K, [&](auto KK) {
+            return launch<head_bwd_kernel<KK>>(dim3(nblk), dim3(EW_BLOCK), 0, st, x, w, dy, dx, (size_t)M, C, partial);
+        });
     } else {
         nblk = ew_blocks((size_t)M / 4 + 1);
-        K_SWITCH(K, hipLaunchKernelGGL(head_bwd_generic_kernel<KK>, dim3(nblk), dim3(EW_BLOCK), 0, st, x, w, dy, dx, (size_t)M, C, partial));
+        e = with_k(K, [&](auto KK) {
+            return launch<head_bwd_generic_kernel<KK>>(dim3(nblk), dim3(EW_BLOCK), 0, st, x, w, dy, dx, (size_t)M, C, partial);
+        });
     }
-    VNET_LAUNCH_CHECK();
-    hipLaunchKernelGGL(head_finalize_kernel, dim3(C * K + K), dim3(256), 0, st, partial, nblk, C * K, K, dw, db);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    if (e) return e;
+    return launch<head_finalize_kernel>(dim3(C * K + K), dim3(256), 0, st, partial, nblk, C * K, K, dw, db);
 }
 
 int vnet_softmax_dice_fwd(const float* logits, const int32_t* labels, int B, int64_t V, int K,
@@ -1943,13 +1916,10 @@ int vnet_softmax_dice_fwd(const float* logits, const int32_t* labels, int B, int
     p.pred_out = (long long*)pred_out; p.partial = (float*)ws; p.V = (size_t)V; p.B = B; p.K = K; p.kind = loss_kind;
     const int nblk = ew_blocks((size_t)V / 4 + 1);
     p.nblk = nblk;
-    K_SWITCH(K, hipLaunchKernelGGL(softmax_dice_fwd_kernel<KK>, dim3(nblk, B), dim3(EW_BLOCK), 0, st, p));
-    VNET_LAUNCH_CHECK();
+    if (int e = with_k(K, [&](auto KK) { return launch<softmax_dice_fwd_kernel<KK>>(dim3(nblk, B), dim3(EW_BLOCK), 0, st, p); })) return e;
     double* sums = reinterpret_cast<double*>((char*)ws + align_up((size_t)B * EW_MAXBLK * (3 * K + 1) * sizeof(float), 16));
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1024), 0, st, p.partial, nblk, sums, B, K, (double)V, loss_kind, weights, alpha,
-                       smooth, loss_out, dice_out, coef);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<loss_finalize_kernel>(dim3(1), dim3(1024), 0, st, p.partial, nblk, sums, B, K, (double)V, loss_kind, weights, alpha,
+                                        smooth, loss_out, dice_out, coef);
 }
 
 int vnet_softmax_dice_bwd(const float* logits, const int32_t* labels, int B, int64_t V, int K,
@@ -1960,10 +1930,10 @@ int vnet_softmax_dice_bwd(const float* logits, const int32_t* labels, int B, int
     if (B * K > 64 || B > 8) return VNET_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = ew_blocks((size_t)V / 4 + 1);
-    K_SWITCH(K, hipLaunchKernelGGL(softmax_dice_bwd_kernel<KK>, dim3(nblk, B), dim3(EW_BLOCK), 0, st, logits, labels, (size_t)V,
-                                   loss_kind, weights, coef, B, gscale, dlogits));
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return with_k(K, [&](auto KK) {
+        return launch<softmax_dice_bwd_kernel<KK>>(dim3(nblk, B), dim3(EW_BLOCK), 0, st, logits, labels, (size_t)V, loss_kind, weights, coef,
+                                                   B, gscale, dlogits);
+    });
 }
 
 int vnet_dice_coe_fwd(const float* output, const float* target, int B, int64_t V, int K, int jaccard,
@@ -1977,55 +1947,45 @@ int vnet_dice_coe_fwd(const float* output, const float* target, int B, int64_t V
     double* sums = reinterpret_cast<double*>((char*)ws + align_up((size_t)B * EW_MAXBLK * (3 * K + 1) * sizeof(float), 16));
     float* loss_tmp = reinterpret_cast<float*>(sums + (size_t)B * (3 * K + 1));
     const int nblk = ew_blocks((size_t)V / 4 + 1);
-    K_SWITCH(K, hipLaunchKernelGGL(dice_sums_kernel<KK>, dim3(nblk, B), dim3(EW_BLOCK), 0, st, output, target, (size_t)V, jaccard, partial));
-    VNET_LAUNCH_CHECK();
+    if (int e = with_k(K, [&](auto KK) {
+            return launch<dice_sums_kernel<KK>>(dim3(nblk, B), dim3(EW_BLOCK), 0, st, output, target, (size_t)V, jaccard, partial);
+        }))
+        return e;
     const int kind = (jaccard ? VNET_LOSS_JACCARD : VNET_LOSS_SORENSEN) | (weights ? VNET_LOSS_WEIGHTED : 0);
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1024), 0, st, partial, nblk, sums, B, K, (double)V, kind, weights, 0.f,
-                       smooth, loss_tmp, dice_out, coef);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<loss_finalize_kernel>(dim3(1), dim3(1024), 0, st, partial, nblk, sums, B, K, (double)V, kind, weights, 0.f,
+                                        smooth, loss_tmp, dice_out, coef);
 }
 
 int vnet_dice_coe_bwd(const float* output, const float* target, int B, int64_t V, int K, int jaccard,
                       const float* coef, const float* gscale, float* doutput, void* stream) {
     if (!output || !target || !coef || !doutput || B <= 0 || V <= 0 || K <= 0) return VNET_E_BADARG;
-    hipLaunchKernelGGL(dice_grad_kernel, dim3(ew_blocks((size_t)V * K / 4 + 1), B), dim3(EW_BLOCK), 0, (hipStream_t)stream,
-                       output, target, (size_t)V, K, jaccard, coef, gscale, doutput);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<dice_grad_kernel>(dim3(ew_blocks((size_t)V * K / 4 + 1), B), dim3(EW_BLOCK), 0, (hipStream_t)stream,
+                                    output, target, (size_t)V, K, jaccard, coef, gscale, doutput);
 }
 
 int vnet_step_state_set(void* state, float lr, float lr_t, uint64_t step, void* stream) {
     if (!state) return VNET_E_BADARG;
-    hipLaunchKernelGGL(step_state_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (StepState*)state, lr, lr_t, step);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<step_state_kernel>(dim3(1), dim3(1), 0, (hipStream_t)stream, (StepState*)state, lr, lr_t, step);
 }
 
 int vnet_dropout_fwd_dev(const float* x, float* y, uint8_t* mask, int64_t n, float rate, uint64_t seed, const void* state, void* stream) {
     if (!x || !y || !mask || n <= 0 || rate < 0.f || rate >= 1.f) return VNET_E_BADARG;
-    hipLaunchKernelGGL(dropout_fwd_kernel, dim3(ew_blocks((size_t)n / 4 + 1)), dim3(EW_BLOCK), 0, (hipStream_t)stream, x, y, mask, (size_t)n, rate, seed,
-                       (const StepState*)state, (__bf16*)nullptr);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<dropout_fwd_kernel>(dim3(ew_blocks((size_t)n / 4 + 1)), dim3(EW_BLOCK), 0, (hipStream_t)stream, x, y, mask, (size_t)n, rate, seed,
+                                      (const StepState*)state, (__bf16*)nullptr);
 }
 int vnet_dropout_fwd(const float* x, float* y, uint8_t* mask, int64_t n, float rate, uint64_t seed, void* stream) {
     return vnet_dropout_fwd_dev(x, y, mask, n, rate, seed, nullptr, stream);
 }
 int vnet_dropout_bwd(const float* dy, const uint8_t* mask, float* dx, int64_t n, float rate, void* stream) {
     if (!dy || !dx || !mask || n <= 0 || rate < 0.f || rate >= 1.f) return VNET_E_BADARG;
-    hipLaunchKernelGGL(dropout_bwd_kernel, dim3(ew_blocks((size_t)n / 4 + 1)), dim3(EW_BLOCK), 0, (hipStream_t)stream, dy, mask, dx, (size_t)n, rate);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<dropout_bwd_kernel>(dim3(ew_blocks((size_t)n / 4 + 1)), dim3(EW_BLOCK), 0, (hipStream_t)stream, dy, mask, dx, (size_t)n, rate);
 }
 
 static int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, const void* state,
                        float beta1, float beta2, float eps, float gscale, void* stream) {
     if (!p || !g || !m || !v || n <= 0) return VNET_E_BADARG;
-    hipLaunchKernelGGL(adam_kernel, dim3(ew_blocks((size_t)n / 4 + 1) * 2), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, g, m, v, (size_t)n,
-                       lr_t, beta1, beta2, eps, gscale, (const StepState*)state);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<adam_kernel>(dim3(ew_blocks((size_t)n / 4 + 1) * 2), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, g, m, v, (size_t)n,
+                               lr_t, beta1, beta2, eps, gscale, (const StepState*)state);
 }
 int vnet_adam_apply(float* p, const float* g, float* m, float* v, int64_t n,
                     float lr_t, float beta1, float beta2, float eps, float gscale, void* stream) {
@@ -2038,10 +1998,8 @@ int vnet_adam_apply_dev(float* p, const float* g, float* m, float* v, int64_t n,
 }
 static int sgd_launch(float* p, const float* g, int64_t n, float lr, const void* state, float gscale, void* stream) {
     if (!p || !g || n <= 0) return VNET_E_BADARG;
-    hipLaunchKernelGGL(sgd_kernel, dim3(ew_blocks((size_t)n / 4 + 1) * 2), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, g, (size_t)n, lr, gscale,
-                       (const StepState*)state);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<sgd_kernel>(dim3(ew_blocks((size_t)n / 4 + 1) * 2), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, g, (size_t)n, lr, gscale,
+                              (const StepState*)state);
 }
 int vnet_sgd_apply(float* p, const float* g, int64_t n, float lr, float gscale, void* stream) {
     return sgd_launch(p, g, n, lr, nullptr, gscale, stream);
@@ -2053,10 +2011,8 @@ int vnet_sgd_apply_dev(float* p, const float* g, int64_t n, const void* state, f
 static int momentum_launch(float* p, const float* g, float* acc, int64_t n, float lr, const void* state, float momentum,
                            int nesterov, float gscale, void* stream) {
     if (!p || !g || !acc || n <= 0) return VNET_E_BADARG;
-    hipLaunchKernelGGL(momentum_kernel, dim3(ew_blocks((size_t)n / 4 + 1) * 2), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, g, acc, (size_t)n,
-                       lr, momentum, nesterov, gscale, (const StepState*)state);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<momentum_kernel>(dim3(ew_blocks((size_t)n / 4 + 1) * 2), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, g, acc, (size_t)n,
+                                   lr, momentum, nesterov, gscale, (const StepState*)state);
 }
 int vnet_momentum_apply(float* p, const float* g, float* acc, int64_t n, float lr, float momentum,
                         int nesterov, float gscale, void* stream) {
@@ -2071,10 +2027,8 @@ int vnet_momentum_apply_dev(float* p, const float* g, float* acc, int64_t n, con
 int vnet_accumulate_patch(const float* patch, float* vol, float* count, int K,
                           int pz, int py, int px, int z0, int y0, int x0, int D, int H, int W, void* stream) {
     if (!patch || !vol || K <= 0 || pz <= 0 || py <= 0 || px <= 0 || z0 < 0 || y0 < 0 || x0 < 0) return VNET_E_BADARG;
-    hipLaunchKernelGGL(accumulate_patch_kernel, dim3(ew_blocks((size_t)pz * py * px)), dim3(EW_BLOCK), 0, (hipStream_t)stream,
-                       patch, vol, count, K, pz, py, px, z0, y0, x0, D, H, W);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<accumulate_patch_kernel>(dim3(ew_blocks((size_t)pz * py * px)), dim3(EW_BLOCK), 0, (hipStream_t)stream,
+                                           patch, vol, count, K, pz, py, px, z0, y0, x0, D, H, W);
 }
 
 // ---- bf16-storage entry points -------------------------------------------------------------------------------------------
@@ -2085,19 +2039,15 @@ static inline int b16_blocks(size_t n8) { return ew_blocks(n8 / 2 + 1); }       
 int vnet_cast_bf16(const float* x, void* y16, int64_t M, int C, int Cpad, void* stream) {
     if (!x || !y16 || M <= 0 || C <= 0 || Cpad < C) return VNET_E_BADARG;
     if ((Cpad & 7) || !al16(y16)) return VNET_E_UNSUPPORTED;
-    hipLaunchKernelGGL(cast_pad_bf16_kernel, dim3(ew_blocks((size_t)M * (Cpad / 8) / 2 + 1)), dim3(EW_BLOCK), 0, (hipStream_t)stream,
-                       x, reinterpret_cast<u32x4*>(y16), (size_t)M, C, Cpad);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<cast_pad_bf16_kernel>(dim3(ew_blocks((size_t)M * (Cpad / 8) / 2 + 1)), dim3(EW_BLOCK), 0, (hipStream_t)stream,
+                                        x, reinterpret_cast<u32x4*>(y16), (size_t)M, C, Cpad);
 }
 
 static int bn_partial_moments_b16(const void* x16, const void* r16, int64_t M, int C, float* partial, hipStream_t st, int* nblk_out) {
     if (!b16_channels_ok(C) || !al16(x16) || !al16(r16)) return VNET_E_UNSUPPORTED;
     BnP16 p{}; p.x = x16; p.r = r16; p.M = (size_t)M; p.C = C; p.partial = partial;
     const int nblk = b16_blocks((size_t)M * (C / 8));
-    if (r16) hipLaunchKernelGGL(bn_stats_b16_kernel<true>, dim3(nblk), dim3(EW_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL(bn_stats_b16_kernel<false>, dim3(nblk), dim3(EW_BLOCK), 0, st, p);
-    VNET_LAUNCH_CHECK();
+    if (int e = with_bool(r16, [&](auto R) { return launch<bn_stats_b16_kernel<R>>(dim3(nblk), dim3(EW_BLOCK), 0, st, p); })) return e;
     *nblk_out = nblk;
     return VNET_OK;
 }
@@ -2110,10 +2060,8 @@ int vnet_bn_stats_b16(const void* x16, const void* r16, int64_t M, int C, float 
     int nblk;
     const int rc = bn_partial_moments_b16(x16, r16, M, C, (float*)ws, st, &nblk);
     if (rc != VNET_OK) return rc;
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, st, (const float*)ws, nblk, C, C, (double)M, eps, momentum,
-                       mean, invstd, moving_mean, moving_var);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<bn_finalize_kernel>(dim3(C), dim3(256), 0, st, (const float*)ws, nblk, C, C, (double)M, eps, momentum,
+                                      mean, invstd, moving_mean, moving_var);
 }
 
 // per-channel sum of a bf16 [M][C] tensor into fp32 (the bias gradient of a bf16-storage convolution outside the networks' closed
@@ -2157,11 +2105,8 @@ int vnet_colsum_b16(const void* x16, float* out, int64_t M, int C, void* ws, siz
     hipStream_t st = (hipStream_t)stream;
     const int CO = C / 8, RB = 256 / CO;
     const int nblk = (int)min((int64_t)1024, (M + RB - 1) / RB);
-    hipLaunchKernelGGL(colsum_b16_kernel, dim3(nblk), dim3(256), 0, st, reinterpret_cast<const u32x4*>(x16), (size_t)M, CO, (float*)ws);
-    VNET_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sum_finalize_kernel<float>, dim3(C), dim3(256), 0, st, (const float*)ws, nblk, 1, C, out, (float*)nullptr, (float*)nullptr);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    if (int e = launch<colsum_b16_kernel>(dim3(nblk), dim3(256), 0, st, reinterpret_cast<const u32x4*>(x16), (size_t)M, CO, (float*)ws)) return e;
+    return launch<sum_finalize_kernel<float>>(dim3(C), dim3(256), 0, st, (const float*)ws, nblk, 1, C, out, (float*)nullptr, (float*)nullptr);
 }
 
 int vnet_bn_moments_b16(const void* x16, const void* r16, int64_t M, int C, double* sums, void* ws, size_t ws_bytes, void* stream) {
@@ -2171,9 +2116,7 @@ int vnet_bn_moments_b16(const void* x16, const void* r16, int64_t M, int C, doub
     int nblk;
     const int rc = bn_partial_moments_b16(x16, r16, M, C, (float*)ws, st, &nblk);
     if (rc != VNET_OK) return rc;
-    hipLaunchKernelGGL(bn_moments_kernel, dim3(C), dim3(256), 0, st, (const float*)ws, nblk, C, C, sums);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<bn_moments_kernel>(dim3(C), dim3(256), 0, st, (const float*)ws, nblk, C, C, sums);
 }
 
 static int bn16_fill(BnP16& p, const void* dy, const void* x, const void* r, int bcast, int64_t M, int C, const float* mean, const float* invstd,
@@ -2197,11 +2140,9 @@ int vnet_bn_act_fwd_b16(const void* x, const void* r16, int bcast, int64_t M, in
     if (!al16(y16)) return VNET_E_UNSUPPORTED;
     p.out = y16;
     const int nblk = b16_blocks((size_t)M * (C / 8));
-    if (bcast) hipLaunchKernelGGL((bn_act_fwd_b16_kernel<true, false>), dim3(nblk), dim3(EW_BLOCK), 0, (hipStream_t)stream, p);
-    else if (p.r) hipLaunchKernelGGL((bn_act_fwd_b16_kernel<false, true>), dim3(nblk), dim3(EW_BLOCK), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((bn_act_fwd_b16_kernel<false, false>), dim3(nblk), dim3(EW_BLOCK), 0, (hipStream_t)stream, p);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return with_bcast_r(bcast, p.r, [&](auto BC, auto R) {
+        return launch<bn_act_fwd_b16_kernel<BC, R>>(dim3(nblk), dim3(EW_BLOCK), 0, (hipStream_t)stream, p);
+    });
 }
 
 int vnet_bn_act_bwd_reduce_b16(const void* dy16, const void* x, const void* r16, int bcast, int64_t M, int C,
@@ -2217,14 +2158,12 @@ int vnet_bn_act_bwd_reduce_b16(const void* dy16, const void* x, const void* r16,
     hipStream_t st = (hipStream_t)stream;
     p.partial = (float*)ws;
     const int nblk = b16_blocks((size_t)M * (C / 8));
-    if (bcast) hipLaunchKernelGGL((bn_act_bwd_reduce_b16_kernel<true, false>), dim3(nblk), dim3(EW_BLOCK), 0, st, p);
-    else if (p.r) hipLaunchKernelGGL((bn_act_bwd_reduce_b16_kernel<false, true>), dim3(nblk), dim3(EW_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((bn_act_bwd_reduce_b16_kernel<false, false>), dim3(nblk), dim3(EW_BLOCK), 0, st, p);
-    VNET_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sum_finalize_kernel<float>, dim3(C), dim3(256), 0, st, (const float*)p.partial, nblk, 3, C, dbeta, dgamma,
-                       act == VNET_ACT_PRELU ? dalpha : (float*)nullptr);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    if (int e = with_bcast_r(bcast, p.r, [&](auto BC, auto R) {
+            return launch<bn_act_bwd_reduce_b16_kernel<BC, R>>(dim3(nblk), dim3(EW_BLOCK), 0, st, p);
+        }))
+        return e;
+    return launch<sum_finalize_kernel<float>>(dim3(C), dim3(256), 0, st, (const float*)p.partial, nblk, 3, C, dbeta, dgamma,
+                                              act == VNET_ACT_PRELU ? dalpha : (float*)nullptr);
 }
 
 int vnet_bn_act_bwd_apply_b16(const void* dy16, const void* x, const void* r16, int bcast, int64_t M, int C,
@@ -2238,11 +2177,9 @@ int vnet_bn_act_bwd_apply_b16(const void* dy16, const void* x, const void* r16, 
     if (!al16(ds16)) return VNET_E_UNSUPPORTED;
     p.invM = (float)(1.0 / M_total); p.extra = xhat_coef; p.out = ds16; p.dgamma = sum_dz_xhat; p.dbeta = sum_dz;
     const int nblk = b16_blocks((size_t)M * (C / 8));
-    if (bcast) hipLaunchKernelGGL((bn_act_bwd_apply_b16_kernel<true, false>), dim3(nblk), dim3(EW_BLOCK), 0, (hipStream_t)stream, p);
-    else if (p.r) hipLaunchKernelGGL((bn_act_bwd_apply_b16_kernel<false, true>), dim3(nblk), dim3(EW_BLOCK), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((bn_act_bwd_apply_b16_kernel<false, false>), dim3(nblk), dim3(EW_BLOCK), 0, (hipStream_t)stream, p);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return with_bcast_r(bcast, p.r, [&](auto BC, auto R) {
+        return launch<bn_act_bwd_apply_b16_kernel<BC, R>>(dim3(nblk), dim3(EW_BLOCK), 0, (hipStream_t)stream, p);
+    });
 }
 
 // ---- small tensors: one launch per direction (bn_small_*_b16_kernel) ---------------------------------------------------------------
@@ -2258,10 +2195,7 @@ int vnet_bn_small_fwd_b16(const void* x16, const void* r16, int64_t M, int C, fl
     BnSmall p{};
     p.x = (const u32x4*)x16; p.r = (const u32x4*)r16; p.out = (u32x4*)y16; p.gamma = gamma; p.beta = beta; p.alpha = alpha;
     p.mean = mean; p.invstd = invstd; p.mm = moving_mean; p.mv = moving_var; p.M = (int)M; p.C = C; p.act = act; p.eps = eps; p.momentum = momentum;
-    if (r16) hipLaunchKernelGGL(bn_small_fwd_b16_kernel<true>, dim3(C / 8), dim3(EW_BLOCK), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(bn_small_fwd_b16_kernel<false>, dim3(C / 8), dim3(EW_BLOCK), 0, (hipStream_t)stream, p);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return with_bool(r16, [&](auto R) { return launch<bn_small_fwd_b16_kernel<R>>(dim3(C / 8), dim3(EW_BLOCK), 0, (hipStream_t)stream, p); });
 }
 int vnet_bn_small_bwd_b16(const void* dy16, const void* x16, const void* r16, int64_t M, int C,
                           const float* mean, const float* invstd, const float* gamma, const float* beta, int act, const float* alpha,
@@ -2273,10 +2207,7 @@ int vnet_bn_small_bwd_b16(const void* dy16, const void* x16, const void* r16, in
     p.x = (const u32x4*)x16; p.r = (const u32x4*)r16; p.dy = (const u32x4*)dy16; p.out = (u32x4*)ds16; p.gamma = gamma; p.beta = beta; p.alpha = alpha;
     p.mean = const_cast<float*>(mean); p.invstd = const_cast<float*>(invstd); p.dgamma = dgamma; p.dbeta = dbeta; p.dalpha = dalpha;
     p.M = (int)M; p.C = C; p.act = act;
-    if (r16) hipLaunchKernelGGL(bn_small_bwd_b16_kernel<true>, dim3(C / 8), dim3(EW_BLOCK), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(bn_small_bwd_b16_kernel<false>, dim3(C / 8), dim3(EW_BLOCK), 0, (hipStream_t)stream, p);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return with_bool(r16, [&](auto R) { return launch<bn_small_bwd_b16_kernel<R>>(dim3(C / 8), dim3(EW_BLOCK), 0, (hipStream_t)stream, p); });
 }
 
 int vnet_head_fwd_b16(const void* x16, const float* w, const float* bias, float* y, int64_t M, int C, int K, void* stream) {
@@ -2284,9 +2215,9 @@ int vnet_head_fwd_b16(const void* x16, const float* w, const float* bias, float*
     if (C * K > 1024 || (C & 7) || !al16(x16)) return VNET_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = ew_blocks((size_t)M / 2 + 1);
-    K_SWITCH(K, hipLaunchKernelGGL(head_fwd_b16_kernel<KK>, dim3(nblk), dim3(EW_BLOCK), 0, st, (const u32x4*)x16, w, bias, y, (size_t)M, C));
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return with_k(K, [&](auto KK) {
+        return launch<head_fwd_b16_kernel<KK>>(dim3(nblk), dim3(EW_BLOCK), 0, st, (const u32x4*)x16, w, bias, y, (size_t)M, C);
+    });
 }
 
 int vnet_head_bwd_b16(const void* x16, const float* w, const float* dy, void* dx16, float* dw, float* db,
@@ -2297,29 +2228,25 @@ int vnet_head_bwd_b16(const void* x16, const float* w, const float* dy, void* dx
     hipStream_t st = (hipStream_t)stream;
     float* partial = (float*)ws;
     const int nblk = ew_blocks((size_t)M * (C / 8) / 2 + 1);
-    K_SWITCH(K, hipLaunchKernelGGL(head_bwd_b16_kernel<KK>, dim3(nblk), dim3(EW_BLOCK), 0, st, (const u32x4*)x16, w, dy, (u32x4*)dx16,
-                                   (size_t)M, C, partial));
-    VNET_LAUNCH_CHECK();
-    hipLaunchKernelGGL(head_finalize_kernel, dim3(C * K + K), dim3(256), 0, st, partial, nblk, C * K, K, dw, db);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    if (int e = with_k(K, [&](auto KK) {
+            return launch<head_bwd_b16_kernel<KK>>(dim3(nblk), dim3(EW_BLOCK), 0, st, (const u32x4*)x16, w, dy, (u32x4*)dx16, (size_t)M, C,
+                                                   partial);
+        }))
+        return e;
+    return launch<head_finalize_kernel>(dim3(C * K + K), dim3(256), 0, st, partial, nblk, C * K, K, dw, db);
 }
 
 int vnet_dropout_fwd_b16(const void* x16, void* y16, uint8_t* mask, int64_t n, float rate, uint64_t seed, const void* state, void* stream) {
     if (!x16 || !y16 || !mask || n <= 0 || rate < 0.f || rate >= 1.f) return VNET_E_BADARG;
     if ((n & 7) || !al16(x16) || !al16(y16) || (reinterpret_cast<uintptr_t>(mask) & 7)) return VNET_E_UNSUPPORTED;
-    hipLaunchKernelGGL(dropout_fwd_b16_kernel, dim3(ew_blocks((size_t)n / 8 / 2 + 1)), dim3(EW_BLOCK), 0, (hipStream_t)stream,
-                       (const u32x4*)x16, (u32x4*)y16, mask, (size_t)n / 8, rate, seed, (const StepState*)state);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<dropout_fwd_b16_kernel>(dim3(ew_blocks((size_t)n / 8 / 2 + 1)), dim3(EW_BLOCK), 0, (hipStream_t)stream,
+                                          (const u32x4*)x16, (u32x4*)y16, mask, (size_t)n / 8, rate, seed, (const StepState*)state);
 }
 int vnet_dropout_bwd_b16(const void* dy16, const uint8_t* mask, void* dx16, int64_t n, float rate, void* stream) {
     if (!dy16 || !dx16 || !mask || n <= 0 || rate < 0.f || rate >= 1.f) return VNET_E_BADARG;
     if ((n & 7) || !al16(dy16) || !al16(dx16) || (reinterpret_cast<uintptr_t>(mask) & 7)) return VNET_E_UNSUPPORTED;
-    hipLaunchKernelGGL(dropout_bwd_b16_kernel, dim3(ew_blocks((size_t)n / 8 / 2 + 1)), dim3(EW_BLOCK), 0, (hipStream_t)stream,
-                       (const u32x4*)dy16, mask, (u32x4*)dx16, (size_t)n / 8, rate);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<dropout_bwd_b16_kernel>(dim3(ew_blocks((size_t)n / 8 / 2 + 1)), dim3(EW_BLOCK), 0, (hipStream_t)stream,
+                                          (const u32x4*)dy16, mask, (u32x4*)dx16, (size_t)n / 8, rate);
 }
 
 }  // extern "C"

@@ -524,9 +524,7 @@ int vnet_tile_im2col_x(const float* img, float* xv, int B, int D, int H, int W, 
     const size_t nvox = (size_t)B * D * H * W;
     const size_t nq = nvox * 4;
     const int blocks = (int)(nq / 256 / 4 + 1 > 4096 ? 4096 : nq / 256 / 4 + 1);
-    hipLaunchKernelGGL(im2col_x_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, img, xv, nvox, W);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<im2col_x_kernel>(dim3(blocks), dim3(256), 0, (hipStream_t)stream, img, xv, nvox, W);
 }
 
 
@@ -539,9 +537,7 @@ int vnet_input_conv_direct_stats_rows(int B, int D, int H, int W) {
 int vnet_input_conv_fold_border(const float* wv, int O, float* wbc, float* cbc, void* stream) {
     if (!wv || !wbc || !cbc || O <= 0) return VNET_E_BADARG;
     if (O > 16) return VNET_E_UNSUPPORTED;
-    hipLaunchKernelGGL(input_fold_border_kernel, dim3(9), dim3(256), 0, (hipStream_t)stream, wv, O, wbc, cbc);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<input_fold_border_kernel>(dim3(9), dim3(256), 0, (hipStream_t)stream, wv, O, wbc, cbc);
 }
 int vnet_input_conv_direct_fwd(const float* img, const float* wv, const float* wbc, const float* cbc, const float* bias, const float* res,
                                float* y, float* stats, int O, int B, int D, int H, int W, void* stream) {
@@ -549,21 +545,13 @@ int vnet_input_conv_direct_fwd(const float* img, const float* wv, const float* w
     if (O != 16 && O != 8) return VNET_E_UNSUPPORTED;
     ICArgs a{img, wv, wbc, cbc, bias, res, y, stats, B, D, H, W, ceil_div(D, IC_TZ), ceil_div(H, IC_TY), ceil_div(W, IC_TX)};
     const int grid = B * a.nbz * a.nby * a.nbx;
-    if (O == 16) hipLaunchKernelGGL(input_conv_direct_kernel<16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(input_conv_direct_kernel<8>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return with_int<16, 8>(O, [&](auto OC) { return launch<input_conv_direct_kernel<OC>>(dim3(grid), dim3(256), 0, (hipStream_t)stream, a); });
 }
 // workgroups (= partial slabs [25][16][O] floats) of the direct filter gradient; ws must hold that many slabs
-static int device_cus_ib() {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    return n;
-}
 int vnet_input_wgrad_direct_slabs(int B, int D, int H, int W) {
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
     const int nbrick = B * ceil_div(D, IW_TZ) * ceil_div(H, IC_TY) * ceil_div(W, IC_TX);
-    const int cap = 2 * device_cus_ib();              // two workgroups per CU (49 KB of LDS each; 256 registers per lane)
+    const int cap = 2 * device_cus();                 // two workgroups per CU (49 KB of LDS each; 256 registers per lane)
     return nbrick < cap ? nbrick : cap;
 }
 int vnet_input_wgrad_direct(const float* img, const float* dy, float* G, int O, int B, int D, int H, int W, void* ws, size_t ws_bytes, void* stream) {
@@ -576,39 +564,27 @@ int vnet_input_wgrad_direct(const float* img, const float* dy, float* G, int O, 
     float* part = reinterpret_cast<float*>(ws);
     const size_t lds = (size_t)(IW_TILE + (IW_TZ * IC_TY + 1) * 5 * 16 + IW_NVB * 16) * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
-    if (O == 16) {
-        static bool done = false;
-        if (!done) { if (hipFuncSetAttribute((const void*)input_wgrad_direct_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return VNET_E_UNSUPPORTED; done = true; }
-        hipLaunchKernelGGL(input_wgrad_direct_kernel<16>, dim3(grid), dim3(256), lds, st, img, dy, part, B, D, H, W, nbz, nby, nbx);
-    } else {
-        static bool done = false;
-        if (!done) { if (hipFuncSetAttribute((const void*)input_wgrad_direct_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return VNET_E_UNSUPPORTED; done = true; }
-        hipLaunchKernelGGL(input_wgrad_direct_kernel<8>, dim3(grid), dim3(256), lds, st, img, dy, part, B, D, H, W, nbz, nby, nbx);
-    }
-    VNET_LAUNCH_CHECK();
-    hipLaunchKernelGGL(input_wgrad_reduce_kernel, dim3(ceil_div(n, 64)), dim3(256), 0, st, part, grid, n, G);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    if (int e = with_int<16, 8>(O, [&](auto OC) {
+            return launch<input_wgrad_direct_kernel<OC>>(dim3(grid), dim3(256), lds, st, img, dy, part, B, D, H, W, nbz, nby, nbx);
+        }))
+        return e;
+    return launch<input_wgrad_reduce_kernel>(dim3(ceil_div(n, 64)), dim3(256), 0, st, part, grid, n, G);
 }
 
 int vnet_input_conv_fold(const float* w, const float* gamma, const float* beta, const float* mean, const float* invstd,
                          float* wv, int C, int O, void* stream) {
     if (!w || !gamma || !beta || !mean || !invstd || !wv || C <= 0 || O <= 0) return VNET_E_BADARG;
     if (O > 16) return VNET_E_UNSUPPORTED;
-    hipLaunchKernelGGL(fold_weights_kernel, dim3(ceil_div(25 * 16 * O, 256)), dim3(256), 0, (hipStream_t)stream,
-                       w, gamma, beta, mean, invstd, wv, C, O);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<fold_weights_kernel>(dim3(ceil_div(25 * 16 * O, 256)), dim3(256), 0, (hipStream_t)stream,
+                                       w, gamma, beta, mean, invstd, wv, C, O);
 }
 
 int vnet_input_conv_grads(const float* G, const float* w, const float* gamma, const float* beta, const float* mean,
                           const float* invstd, float* dw, float* dgamma, float* dbeta, int C, int O, int accumulate, void* stream) {
     if (!G || !w || !gamma || !beta || !mean || !invstd || !dw || !dgamma || !dbeta || C <= 0 || O <= 0) return VNET_E_BADARG;
     if (O > 16) return VNET_E_UNSUPPORTED;
-    hipLaunchKernelGGL(input_grads_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, G, w, gamma, beta, mean, invstd,
-                       dw, dgamma, dbeta, C, O, accumulate);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<input_grads_kernel>(dim3(C), dim3(256), 0, (hipStream_t)stream, G, w, gamma, beta, mean, invstd,
+                                      dw, dgamma, dbeta, C, O, accumulate);
 }
 
 }  // extern "C"
@@ -684,13 +660,10 @@ int vnet_auc_histogram(const float* softmax, const int32_t* labels, int64_t n, i
     const int64_t want = (n + 256 * 16 - 1) / (256 * 16);
     const int nblk = (int)(want > 256 ? 256 : want);
     const size_t lds = (size_t)(2 * (T + 1) + T) * 4;
-    hipLaunchKernelGGL(auc_hist_kernel, dim3(nblk), dim3(256), lds, (hipStream_t)stream, softmax, labels, (size_t)n, K, cls, thresholds, T,
-                       (unsigned int*)ws);
-    VNET_LAUNCH_CHECK();
+    if (int e = launch<auc_hist_kernel>(dim3(nblk), dim3(256), lds, (hipStream_t)stream, softmax, labels, (size_t)n, K, cls, thresholds, T,
+                                        (unsigned int*)ws)) return e;
     const int W = 2 * (T + 1);
-    hipLaunchKernelGGL(auc_hist_finalize_kernel, dim3((W + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const unsigned int*)ws, nblk, W, hist_out);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    return launch<auc_hist_finalize_kernel>(dim3((W + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const unsigned int*)ws, nblk, W, hist_out);
 }
 
 size_t vnet_confusion_ws_bytes(int K) { return (size_t)1024 * K * K * sizeof(float); }
@@ -701,10 +674,9 @@ int vnet_confusion_matrix(const int64_t* pred, const int32_t* labels, int64_t n,
     if (K > 8) return VNET_E_UNSUPPORTED;
     if (!ws || ws_bytes < vnet_confusion_ws_bytes(K)) return VNET_E_WORKSPACE;
     const int nblk = (int)((n + 256 * 16 - 1) / (256 * 16) > 1024 ? 1024 : (n + 256 * 16 - 1) / (256 * 16));
-    hipLaunchKernelGGL(confusion_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const long long*)pred, labels, (size_t)n, K, (float*)ws);
-    VNET_LAUNCH_CHECK();
-    hipLaunchKernelGGL(confusion_finalize_kernel, dim3(K * K), dim3(256), 0, (hipStream_t)stream, (const float*)ws, nblk, K * K, cm_out);
-    VNET_LAUNCH_CHECK();
-    return VNET_OK;
+    if (int e = launch<confusion_kernel>(dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const long long*)pred, labels, (size_t)n, K,
+                                         (float*)ws))
+        return e;
+    return launch<confusion_finalize_kernel>(dim3(K * K), dim3(256), 0, (hipStream_t)stream, (const float*)ws, nblk, K * K, cm_out);
 }
 }  // extern "C"

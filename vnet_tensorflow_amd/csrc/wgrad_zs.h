@@ -322,18 +322,10 @@ inline int zs_geometry(WgradArgs& a) {
     return a.nbrick;
 }
 
-template <int TX>
-int launch_wgrad_zs_t(const WgradArgs& a, hipStream_t st) {
-    auto k = wgrad5_b16_zs_kernel<TX>;
-    static unsigned long long attr_done = 0;
-    if (int ae = ensure_lds(k, ZsGeom<TX>::LDS, attr_done)) return ae;
-    dim3 grid(a.nsplit, (a.CinP / 16) * a.ncob, 1);
-    hipLaunchKernelGGL(k, grid, dim3(512), ZsGeom<TX>::LDS, st, a);
-    return (int)hipGetLastError();
-}
 inline int launch_wgrad_zs(const WgradArgs& a, hipStream_t st) {
-    const int tx = zs_tx(a.Wo);
-    return tx == 32 ? launch_wgrad_zs_t<32>(a, st) : tx == 16 ? launch_wgrad_zs_t<16>(a, st) : launch_wgrad_zs_t<8>(a, st);
+    return with_int<32, 16, 8>(zs_tx(a.Wo), [&](auto TX) {
+        return launch<wgrad5_b16_zs_kernel<TX>>(dim3(a.nsplit, (a.CinP / 16) * a.ncob, 1), dim3(512), ZsGeom<TX>::LDS, st, a);
+    });
 }
 
 }  // namespace
