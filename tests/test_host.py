@@ -302,3 +302,38 @@ def test_kernels_launch_only_through_the_launch_helper():
     assert not offenders, offenders
     helper = open(os.path.join(csrc, "common.h")).read()
     assert helper.count("hipLaunchKernelGGL") == 1 and helper.count("hipFuncSetAttribute") == 1
+
+
+def test_guard_band_ledger_has_no_holes():
+    """Every declared entry point with a pointer parameter other than `stream` / `const char*` is run inside a guarded arena by a
+    case of tests/test_hip_guard_bands.py (COVERED = {entry point: [case ids]}) or is in its EXEMPT = {entry point: reason}; no name
+    in either that the header no longer declares; EXEMPT holds no convolution, filter-gradient, input-block, batch-norm, head or
+    loss entry point.  Every family ops.route() returns and every BnRoute statistics source in tests/test_routing.py's tables is
+    taken by a case."""
+    from tests import guard
+    from tests import test_hip_guard_bands as G
+    from tests import test_routing as R
+    table = set(guard.pointer_entry_points())
+    assert len(table) > 60 and "vnet_conv_fwd" in table and "vnet_wgrad_flush" not in table
+    covered, exempt = set(G.COVERED), set(G.EXEMPT)
+    assert not covered & exempt, sorted(covered & exempt)
+    assert not table - covered - exempt, "entry points in neither COVERED nor EXEMPT: %s" % sorted(table - covered - exempt)
+    assert not (covered | exempt) - table, "names the header does not declare: %s" % sorted((covered | exempt) - table)
+    assert all(G.COVERED[e] and all(c in G.CASES for c in G.COVERED[e]) for e in covered)
+    assert all(isinstance(r, str) and r.strip() for r in G.EXEMPT.values())
+    barred = [e for e in exempt if re.search(r"conv|wgrad|input|_bn_|head|softmax|dice|loss", e)]
+    assert not barred, "no exemption for these classes: %s" % barred
+    # the kernels excused from the bit-identity check are exactly the ones that add floats with atomicAdd
+    src = open(os.path.join(ROOT, "vnet_tensorflow_amd", "csrc", "elementwise.hip")).read()
+    atomic, kernel = set(), None
+    for line in src.splitlines():
+        m = re.search(r"__global__ void (?:__launch_bounds__\(\w+\) )?(\w+)\(", line)
+        if m:
+            kernel = m.group(1)
+        if "atomicAdd(" in line:
+            atomic.add(kernel)
+    assert atomic == set(G.ATOMIC_KERNELS), atomic ^ set(G.ATOMIC_KERNELS)
+    families = set(row[2] for rows in R.EXPECTED.values() for row in rows)
+    sources = set(row[7] for rows in R.BN_EXPECTED.values() for row in rows)
+    assert {"conv", "conv-x3", "conv-bf16", "wgrad"} <= families and {"stream", "epilogue"} <= sources
+    assert not (families | sources) - G.FAMILIES, "routes no guarded case takes: %s" % sorted((families | sources) - G.FAMILIES)
