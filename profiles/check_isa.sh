@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/../vnet_tensorflow_amd/csrc"
 OUT=${1:-../../profiles/r06_check_isa.txt}
 TMP=$(mktemp -d)
-for f in conv_mfma conv_x3 conv_b16 conv2_b16 elementwise input_block; do
+for f in conv_mfma conv_x3 conv_b16 conv2_b16 elementwise input_block pool; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-function -Wno-unused-result -S --cuda-device-only $f.hip -o $TMP/$f.s 2>/dev/null &
 done
 wait
@@ -50,6 +50,8 @@ print("convolution kernels with VGPR spills or scratch instructions: %d" % bad)
 sys.exit(1 if bad else 0)
 PY
 rc=$?
+# ISA_KEEP=<dir>: keep the .s files there (profiles/isa_diff.py compares two such directories kernel by kernel)
+if [ -n "$ISA_KEEP" ]; then mkdir -p "$ISA_KEEP" && cp "$TMP"/*.s "$ISA_KEEP"/; fi
 rm -rf "$TMP"
 tail -1 "$OUT"
 exit $rc

@@ -1,4 +1,4 @@
-"""ctypes binding of libvnet_hip.so (include/vnet_hip.h).
+"""ctypes binding of libvnet_hip.so (include/vnet_hip.h, include/vnet_hip_unet.h).
 
 The library is the product: there is NO fallback.  If the shared object is missing, or a
 kernel reports an error, this module raises -- nothing silently routes to PyTorch or the CPU.
@@ -125,6 +125,13 @@ SIGNATURES = {
     "vnet_dropout_bwd_b16": (_i, [_vp, _vp, _vp, _i64, _f, _vp]),
 }
 
+# second public header, include/vnet_hip_unet.h (the U-Net's max-pooling): name -> (restype, argtypes), same library
+SIGNATURES_UNET = {
+    "vnet_maxpool2_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "vnet_maxpool2_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+}
+
+
 class WgradJob(ctypes.Structure):
     """include/vnet_hip.h: vnet_wgrad_job (one layer of vnet_conv_wgrad_b16_group)."""
     _fields_ = [("x0", ctypes.c_void_p), ("x1", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("dw", ctypes.c_void_p),
@@ -181,6 +188,9 @@ def lib():
                 setattr(L, name, _memo(fn, (b"BF16_DEEP", b"BF16_DEEP_TARGET"), L))     # (the kernel choice follows these options)
             elif name.endswith("_ws_bytes") or name.endswith("_stats_rows") or name == "vnet_conv_stats_from_reduce" or name == "vnet_packed_weight_floats":
                 setattr(L, name, _memo(fn))    # pure size queries, asked before every launch: answer repeats from a dict
+        for name, (res, args) in SIGNATURES_UNET.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
         _lib = L
     return _lib
 

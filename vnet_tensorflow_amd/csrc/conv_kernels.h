@@ -307,7 +307,7 @@ __global__ void __launch_bounds__(WAVES * 64) conv_kernel(ConvArgs a) {
     // 2^3 / transposed kernels: a brick has only 8 (1) taps of MFMA work per chunk, so an L2 round trip per tap in front of
     // its MFMAs would dominate.  The first RG taps' weight fragments are issued BEFORE the tile staging (in flight together
     // with the tile's HBM loads), the rest stream through the same RG-slot ring RG taps ahead.
-    constexpr int T3G = KS * KS * KS, RG = (KS == 5) ? 1 : (T3G < 4 ? T3G : 4);
+    constexpr int T3G = KS * KS * KS, RG = (KS == 5 || KS == 3) ? 1 : (T3G < 4 ? T3G : 4);
     for (int chunk = c_begin; chunk < c_end; ++chunk) {
         const float4* wq = a.wp + ((size_t)(chunk * 4 + kk) * a.CoutP + co0 + i);
         float4 wg[RG][NS];
@@ -327,12 +327,13 @@ __global__ void __launch_bounds__(WAVES * 64) conv_kernel(ConvArgs a) {
 #pragma unroll
             for (int n = 0; n < NS; ++n) wg[0][n] = wq[n * 16];
         }
-        if constexpr (KS == 5) {
+        if constexpr (KS == 5 || KS == 3) {
             // Weight fragments come straight from L2 (the whole filter is shared by every workgroup), so
-            // they are software-pipelined PF taps ahead through a 5-slot register ring (5 | 25 taps per
+            // they are software-pipelined PF taps ahead through a KS-slot register ring (5 | 25 resp. 3 | 9 taps per
             // dz slab keeps every ring index a compile-time constant) -- the L2 round trip hides under
             // the MFMAs of the taps in between instead of stalling each tap.
-            constexpr int T2 = KS * KX, T3 = T2 * KS, R = 5, PF = (NS == 1) ? 3 : 1;
+            constexpr int T2 = KS * KX, T3 = T2 * KS, R = KS, PF = (NS == 1) ? (KS == 5 ? 3 : 2) : 1;
+            static_assert(PF < R, "a prefetched slot must not be the one in use");
             static_assert(T2 % R == 0, "ring slots must tile a dz slab");
             float4 wf[R][NS];
             float4 xf[R][MS];     // B fragments ride the same ring one tap ahead (LDS latency off the MFMA path)
@@ -1107,6 +1108,10 @@ ConvPlan plan_conv(int ks, int stride, int up, int Cin, int Cout, int B, int Do,
     // 2^3 stride-2 conv, W >= 16: 1x4x16 output bricks (32 KB input tile, four workgroups per CU) instead of 2x4x16: these launches are
     // load latency / bandwidth, more tiles in flight per CU help (128^3 -> 64^3: 47.8 -> 38.8 us, profiles/bench_updown.py)
     if (stride == 2 && !up) { if (p.small) brick_counts<2, 8, 8>(Do, Ho, Wo, p); else brick_counts<1, 4, 16>(Do, Ho, Wo, p); }
+    else if (ks == 3 && !up) {      // 3^3 stride-1 (U-Net): the 4-wave bricks of the 5^3 kernels -- 38 KB / 14 KB tiles, several workgroups per CU
+        if (Do <= 4 && Ho <= 4 && Wo <= 4 && Cin >= 32) { p.half = 2; brick_counts<4, 4, 4>(Do, Ho, Wo, p); }
+        else { p.half = 1; brick_counts<4, 8, 8>(Do, Ho, Wo, p); }
+    }
     else if (ks == 5 && !up && !p.small) { p.half = 1; brick_counts<4, 8, 8>(Do, Ho, Wo, p); }
     else if (ks == 5 && !up && tuning().f32_small >= 2 && Do <= 4 && Ho <= 4 && Wo <= 4 && Cin >= 32) { p.half = 2; brick_counts<4, 4, 4>(Do, Ho, Wo, p); }      // (Cin >= 32: never the 5x5x1 input block)
     else if (ks == 5 && !up && tuning().f32_small >= 1) { p.half = 1; brick_counts<4, 8, 8>(Do, Ho, Wo, p); }
@@ -1115,7 +1120,7 @@ ConvPlan plan_conv(int ks, int stride, int up, int Cin, int Cout, int B, int Do,
     const int nchunks = round_up(Cin, 16) / 16;
     // deep levels have few bricks: prefer more, narrower cout blocks (each a full workgroup of equal work) until
     // bricks x cout-blocks x channel-chunks fills the 256 CUs in one round, before resorting to tap splits
-    if (ks == 5 && !up) {
+    if ((ks == 5 || ks == 3) && !up) {
         const long nb = (long)B * p.nbz * p.nby * p.nbx;
         const int ncob1 = p.ns * p.ncob;                      // cout blocks at NS = 1
         // (4x4x4 bricks: a workgroup is four waves with one 16-voxel subtile each and a 32 KB tile -- several share a CU, so aim for two
@@ -1149,7 +1154,7 @@ ConvPlan plan_conv(int ks, int stride, int up, int Cin, int Cout, int B, int Do,
     if (!up && nwg < 256 && nchunks > 1) p.nsplit = min(nchunks, ceil_div(tgt, nwg));
     p.cps = ceil_div(nchunks, p.nsplit);
     p.nsplit = ceil_div(nchunks, p.cps);
-    p.nz = (ks == 5 && !up && nwg * p.nsplit < nzmin) ? 5 : 1;
+    p.nz = ((ks == 5 || ks == 3) && !up && nwg * p.nsplit < nzmin) ? ks : 1;
     return p;
 }
 
@@ -2556,12 +2561,12 @@ WgradPlan plan_wgrad(int ks, int kx, int stride, int Cin, int Cout, int B, int D
     // the deep ones with few bricks, where twice the (chunk x cout-block) workgroups means half the filter slabs to reduce
     // and a pipeline fill amortised over twice the bricks: +2.5..5 % measured (and the bf16 kernel's 4-block variant does
     // not fit 256 VGPRs next to its prefetch registers)
-    if (ks == 5 && p.ns == 4) p.ns = 2;
+    if ((ks == 5 || ks == 3) && p.ns == 4) p.ns = 2;      // (3^3: 27 taps over 8 waves x 4 slots, the last 5 slots idle)
     p.ncob = CoutP / (16 * p.ns);
     p.small = Wo < 16;
     const int T3 = ks * ks * kx;
-    if (ks == 5) {
-        p.tw = kx == 1 ? 4 : 16 / p.ns;
+    if (ks == 5 || ks == 3) {
+        p.tw = (kx == 1 || ks == 3) ? 4 : 16 / p.ns;
         if (p.small) { p.nbz = ceil_div(Do, 4); p.nby = ceil_div(Ho, 8); p.nbx = ceil_div(Wo, 8); }
         else { p.nbz = ceil_div(Do, 4); p.nby = ceil_div(Ho, 4); p.nbx = ceil_div(Wo, 16); }
     } else {  // ks == 2, stride 2: out brick 2x4x16 / 2x8x8

@@ -125,7 +125,7 @@ int vnet_pack_weights_batched(const void* descs_dev, int n, void* stream) {
 }
 
 size_t vnet_conv_ws_bytes(int ks, int kx, int stride, int up, int Cin, int Cout, int B, int Do, int Ho, int Wo) {
-    (void)kx;
+    if (ks == 3 && (stride != 1 || up || (kx != 0 && kx != 3))) return 0;
     const int gridW = up ? (Wo + 1) / 2 : Wo;
     ConvPlan p = plan_conv(ks, stride, up, Cin, Cout, B, up ? (Do + 1) / 2 : Do, up ? (Ho + 1) / 2 : Ho, gridW, gridW);
     if (p.nsplit * p.nz <= 1) return 0;
@@ -136,9 +136,10 @@ size_t vnet_conv_ws_bytes(int ks, int kx, int stride, int up, int Cin, int Cout,
 // output, channel count that is no multiple of 4, or a split-K reduce whose channel count does not divide 256)
 int vnet_conv_stats_rows(int ks, int kx, int stride, int up, int Cin, int Cy0, int Cy1, int B, int Do, int Ho, int Wo) {
     if (up || Cy1 != 0 || Cy0 <= 0 || (Cy0 & 3) || Cin <= 0 || B <= 0) return 0;
-    const bool is5 = (ks == 5 && stride == 1), isdown = (ks == 2 && stride == 2);
-    if (!is5 && !isdown) return 0;
+    const bool is5 = (ks == 5 && stride == 1), isdown = (ks == 2 && stride == 2), is3 = (ks == 3 && stride == 1);
+    if (!is5 && !isdown && !is3) return 0;
     if (kx == 0) kx = ks;
+    if (is3 && kx != 3) return 0;
     ConvPlan p = plan_conv(ks, stride, 0, Cin, Cy0, B, Do, Ho, Wo, Wo);
     if (p.nsplit * p.nz > 1) {
         if (Cy0 > 256 || 256 % Cy0) return 0;
@@ -151,8 +152,8 @@ int vnet_conv_stats_rows(int ks, int kx, int stride, int up, int Cin, int Cy0, i
 // 1: the statistics of this launch come from the split-K reduce kernel (an HBM-bound pass that already touches every output
 // element: they are free there); 0: from the MFMA kernel's own epilogue (the STATS instantiation)
 int vnet_conv_stats_from_reduce(int ks, int kx, int stride, int Cin, int Cout, int B, int Do, int Ho, int Wo) {
-    const bool is5 = (ks == 5 && stride == 1), isdown = (ks == 2 && stride == 2);
-    if ((!is5 && !isdown) || Cin <= 0 || Cout <= 0 || B <= 0) return 0;
+    const bool is5 = (ks == 5 && stride == 1), isdown = (ks == 2 && stride == 2), is3 = (ks == 3 && stride == 1 && (kx == 0 || kx == 3));
+    if ((!is5 && !isdown && !is3) || Cin <= 0 || Cout <= 0 || B <= 0) return 0;
     ConvPlan p = plan_conv(ks, stride, 0, Cin, Cout, B, Do, Ho, Wo, Wo);
     return p.nsplit * p.nz > 1 ? 1 : 0;
 }
@@ -177,14 +178,15 @@ static int conv_fwd_impl(int ks, int kx, int stride, int up, const float* x0, in
     a.part = nullptr; a.part_stride = 0; a.upO = 0; a.accum = accum; a.res = res; a.stats = stats;
     if (stats && vnet_conv_stats_rows(ks, kx, stride, up, C0 + C1, Cy0, Cy1, B, Do, Ho, Wo) == 0) return VNET_E_UNSUPPORTED;
     const bool is5 = (ks == 5 && stride == 1 && !up), isdown = (ks == 2 && stride == 2 && !up), isup = (ks == 2 && stride == 2 && up);
-    if (!is5 && !isdown && !isup) return VNET_E_UNSUPPORTED;
+    const bool is3 = (ks == 3 && stride == 1 && !up);         // 3^3 SAME (U-Net, reference networks.py:52,57,78,83)
+    if (!is5 && !isdown && !isup && !is3) return VNET_E_UNSUPPORTED;
     if (kx == 0) kx = ks;
     if (kx != ks && !(is5 && kx == 1 && round_up(Cy0 + Cy1, 16) == 16)) return VNET_E_UNSUPPORTED;   // 5x5x1: x-im2col'ed input conv
     if (isup) {
         if (Cy1 != 0) return VNET_E_UNSUPPORTED;
         a.CoutP = round_up(8 * Cy0, 16); a.upO = Cy0; a.pad = 0; a.padx = 0;
     } else {
-        a.CoutP = round_up(a.Cout, 16); a.pad = is5 ? 2 : 0;
+        a.CoutP = round_up(a.Cout, 16); a.pad = is5 ? 2 : is3 ? 1 : 0;
         a.padx = (kx - 1) / 2;
     }
     const int gD = isup ? Di : Do, gH = isup ? Hi : Ho, gW = isup ? Wi : Wo;
@@ -198,7 +200,10 @@ static int conv_fwd_impl(int ks, int kx, int stride, int up, const float* x0, in
         a.part = reinterpret_cast<float*>(ws); a.part_stride = nvox * a.CoutP;
     }
     int e;
-    if (a.stats && nslab == 1) {     // statistics in the conv epilogue: the STATS instantiations (split-K launches take theirs from the reduce)
+    if (is3) {
+        if (a.stats && nslab == 1) e = p.half == 2 ? launch_conv_ns<3, 1, 4, 4, 4, 4, 1, false, 3, true>(a, p, st) : launch_conv_ns<3, 1, 4, 8, 8, 4, 4, false, 3, true>(a, p, st);
+        else e = p.half == 2 ? launch_conv_ns<3, 1, 4, 4, 4, 4, 1, false>(a, p, st) : launch_conv_ns<3, 1, 4, 8, 8, 4, 4, false>(a, p, st);
+    } else if (a.stats && nslab == 1) {     // statistics in the conv epilogue: the STATS instantiations (split-K launches take theirs from the reduce)
         if (is5) {
             if (kx == 1) e = (p.small && !p.half) ? launch_conv_ns<5, 1, 8, 8, 8, 8, 4, false, 1, true>(a, p, st) : launch_conv_ns<5, 1, 4, 8, 8, 4, 4, false, 1, true>(a, p, st);
             else e = p.half == 2 ? launch_conv_ns<5, 1, 4, 4, 4, 4, 1, false, 5, true>(a, p, st)
@@ -298,6 +303,7 @@ int vnet_wgrad_flush(void* stream) {
 
 size_t vnet_wgrad_ws_bytes(int ks, int kx, int stride, int Cin, int Cout, int B, int Do, int Ho, int Wo) {
     if (kx == 0) kx = ks;
+    if (ks == 3 && (stride != 1 || kx != 3)) return 0;
     WgradPlan p = plan_wgrad(ks, kx, stride, Cin, Cout, B, Do, Ho, Wo);
     return (size_t)p.nsplit * ks * ks * kx * round_up(Cin, 16) * round_up(Cout, 16) * sizeof(float);
 }
@@ -308,7 +314,7 @@ int vnet_conv_wgrad(int ks, int kx, int stride, const float* x0, int C0, const f
                     void* ws, size_t ws_bytes, void* stream) {
     if (!x0 || !dy || !dw || C0 <= 0 || Cout <= 0 || B <= 0 || C1 < 0 || (C1 > 0 && !x1)) return VNET_E_BADARG;
     if (Di <= 0 || Hi <= 0 || Wi <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0) return VNET_E_BADARG;
-    if (!((ks == 5 && stride == 1) || (ks == 2 && stride == 2))) return VNET_E_UNSUPPORTED;
+    if (!((ks == 5 && stride == 1) || (ks == 2 && stride == 2) || (ks == 3 && stride == 1))) return VNET_E_UNSUPPORTED;
     if (kx == 0) kx = ks;
     if (kx != ks && !(ks == 5 && kx == 1 && round_up(Cout, 16) == 16)) return VNET_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
@@ -316,7 +322,7 @@ int vnet_conv_wgrad(int ks, int kx, int stride, const float* x0, int C0, const f
     a.x0 = x0; a.x1 = x1; a.C0 = C0; a.C1 = C1; a.Cin = C0 + C1; a.dy = dy; a.Cout = Cout;
     a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.Do = Do; a.Ho = Ho; a.Wo = Wo;
     a.CinP = round_up(a.Cin, 16); a.CoutP = round_up(Cout, 16);
-    a.pad = ks == 5 ? 2 : 0; a.padx = (kx - 1) / 2;
+    a.pad = ks == 5 ? 2 : ks == 3 ? 1 : 0; a.padx = (kx - 1) / 2;
     a.vec_in = (C0 % 4 == 0) && (C1 % 4 == 0); a.vec_dy = (Cout % 4 == 0);
     WgradPlan p = plan_wgrad(ks, kx, stride, a.Cin, Cout, B, Do, Ho, Wo);
     a.ncob = p.ncob; a.nbz = p.nbz; a.nby = p.nby; a.nbx = p.nbx; a.nbrick = p.nbrick; a.nsplit = p.nsplit;
@@ -327,7 +333,10 @@ int vnet_conv_wgrad(int ks, int kx, int stride, const float* x0, int C0, const f
     if (!direct && (!ws || ws_bytes < need)) return VNET_E_WORKSPACE;
     a.part = direct ? dw : reinterpret_cast<float*>(ws);
     int e;
-    if (ks == 5 && kx == 1) {
+    if (ks == 3) {            // 27 taps on 8 waves x 4 slots: the slots past the filter compute tap 0 again and are not stored
+        if (p.small) e = p.ns == 2 ? launch_wgrad<3, 1, 4, 8, 8, 2, 4>(a, p, st) : launch_wgrad<3, 1, 4, 8, 8, 1, 4>(a, p, st);
+        else e = p.ns == 2 ? launch_wgrad<3, 1, 4, 4, 16, 2, 4>(a, p, st) : launch_wgrad<3, 1, 4, 4, 16, 1, 4>(a, p, st);
+    } else if (ks == 5 && kx == 1) {
         e = p.small ? launch_wgrad<5, 1, 4, 8, 8, 1, 4, 1>(a, p, st) : launch_wgrad<5, 1, 4, 4, 16, 1, 4, 1>(a, p, st);
     } else if (ks == 5) {
         if (p.small) {

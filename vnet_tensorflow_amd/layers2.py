@@ -8,6 +8,8 @@ reference layers2.py:59-63  convolution
 reference layers2.py:65-74  deconvolution
 reference layers2.py:78-94  down_convolution / up_convolution
 reference layers2.py:97-99  prelu
+reference networks.py:120   tf.nn.max_pool3d (U-Net)          -> max_pool3d
+reference networks.py:64-65 batch-norm over the decoder concat -> batch_normalization_concat
 """
 import numpy as np
 
@@ -68,8 +70,8 @@ def convolution(x, filter, padding='SAME', strides=None, dilation_rate=None, ini
     s = 1 if strides is None else int(np.atleast_1d(strides)[0])
     if k == 1 and s == 1:
         return ops.head_conv(x, w, b)
-    if not ((k == 5 and s == 1) or (k == 2 and s == 2)):
-        raise NotImplementedError("kernel %d stride %d is not instantiated (V-Net uses 5/1, 2/2, 1/1)" % (k, s))
+    if not ((k == 5 and s == 1) or (k == 2 and s == 2) or (k == 3 and s == 1)):
+        raise NotImplementedError("kernel %d stride %d is not instantiated (V-Net uses 5/1, 2/2, 1/1; U-Net 3/1)" % (k, s))
     # bn_stats / bn_residual (extension): the caller normalises this output (+ residual) next -- see ops.conv
     return ops.conv(x, w, b, k, s, bn_stats=bn_stats, bn_residual=bn_residual)
 
@@ -80,7 +82,30 @@ def convolution_concat(x, skip, filter, bn_stats=False):
     w = get_variable(name='weights', initializer=lambda: xavier_initializer_convolution(shape=filter))
     b = get_variable(name='biases', initializer=lambda: constant_initializer(0, shape=filter[-1]))
     k = _check_filter(filter, get_spatial_rank(x))
+    if k not in (5, 3):
+        raise NotImplementedError("kernel %d is not instantiated for the two-source convolution (V-Net 5, U-Net 3)" % k)
     return ops.conv(x, w, b, k, 1, x1=skip, bn_stats=bn_stats)
+
+
+def max_pool3d(x, ksize=(1, 2, 2, 2, 1), strides=(1, 2, 2, 2, 1), padding='VALID'):
+    """tf.nn.max_pool3d(x, ksize, strides, padding) as the reference's U-Net calls it (networks.py:120): 2/2/VALID only."""
+    if get_spatial_rank(x) != 3:
+        raise NotImplementedError("only 3-D volumes are built (2-D PatchShape is out of scope, SURVEY section 2 row 11)")
+    if list(ksize) != [1, 2, 2, 2, 1]:
+        raise NotImplementedError("max_pool3d: ksize %s is not instantiated (the U-Net uses [1,2,2,2,1])" % (list(ksize),))
+    if list(strides) != [1, 2, 2, 2, 1]:
+        raise NotImplementedError("max_pool3d: strides %s are not instantiated (the U-Net uses [1,2,2,2,1])" % (list(strides),))
+    if padding != 'VALID':
+        raise NotImplementedError("max_pool3d: padding %r is not instantiated (the U-Net uses 'VALID')" % (padding,))
+    return ops.max_pool2(x)
+
+
+def batch_normalization_concat(x, skip):
+    """tf.layers.batch_normalization(tf.concat((x, skip), -1), training=True) (reference networks.py:64-65) without the concat
+    tensor: ONE variable set of C_x + C_skip channels under the next 'batch_normalization[_N]' name, applied to the two halves
+    (ops.bn_concat).  Returns the two normalised halves, which convolution_concat reads as its two sources."""
+    gamma, beta, mm, mv = _bn_variables(int(x.shape[-1]) + int(skip.shape[-1]))
+    return ops.bn_concat(x, skip, gamma, beta, mm, mv)
 
 
 def deconvolution(x, filter, output_shape, strides, padding='SAME'):

@@ -247,6 +247,8 @@ class image2label(object):
         if self.compute_dtype == 'bf16':
             # 'bf16' = bf16 STORAGE (every activation a bf16 tensor); its kernels move 8-channel units whose count is a power of
             # two: fail HERE, not at the first forward
+            if T.get('Networks', {}).get('Name') == "UNet":
+                self._check_unet()
             nch = int(T.get('Networks', {}).get('NumChannel', 16))
             if nch < 8 or nch & (nch - 1):
                 raise SystemExit("ComputeDtype 'bf16' (bf16 storage) needs Networks.NumChannel = 8 * 2^k, got %d; "
@@ -285,6 +287,8 @@ class image2label(object):
         # the shipped JSONs spell it "NumCovolutions" (configs/config.json:29); accept both
         self.num_convolutions = N['NumConvolutions'] if 'NumConvolutions' in N else N['NumCovolutions']
         self.bottom_convolutions = N['BottomConvolutions']
+        if self.network_name == "UNet":
+            self._check_unet()
         O = T['Optimizer']
         self.optimizer_name = O['Name']
         self.initial_learning_rate = O['InitialLearningRate']
@@ -341,10 +345,37 @@ class image2label(object):
                 is_training=True,
                 activation_fn="prelu",
                 device=self.device)
+        elif self.network_name == "UNet":
+            # reference model.py:417-427 (activation_fn="relu"); the 3^3 kernels are fp32: 'fp32_split3' runs on them unchanged
+            self._check_unet()
+            for key, n in (("NumConvolutions", self.num_convolutions), ("BottomConvolutions", self.bottom_convolutions)):
+                if isinstance(n, bool) or not isinstance(n, int):
+                    # (the reference's UNet runs range(NumConvolutions), networks.py:46,72: a V-Net style list ends it)
+                    sys.exit("Invalid Network: Networks.%s must be one integer for Name 'UNet', got %r" % (key, n))
+            self.network = networks.UNet(
+                num_output_channels=self.output_channel_num,
+                dropout_rate=lambda: self.dropout_placeholder,
+                num_channels=self.num_channel,
+                num_levels=self.num_levels,
+                num_convolutions=self.num_convolutions,
+                bottom_convolutions=self.bottom_convolutions,
+                is_training=True,
+                activation_fn="relu",
+                device=self.device)
         else:
             sys.exit("Invalid Network")
         self.network.build(self.input_batch_shape)
         self._print("{}: Core network complete".format(_now()))
+
+    def _check_unet(self):
+        """What Networks.Name "UNet" does not run with: bf16 storage (its kernels are the V-Net's 5^3 / 2^3 set) and more than one
+        rank (the data-parallel step graphs cut the V-Net's backward pass between encoder and decoder)."""
+        if getattr(self, "compute_dtype", "fp32") == "bf16":
+            raise VnetHipError("ComputeDtype 'bf16' with Networks.Name 'UNet' is not built (bf16 storage covers the V-Net's "
+                               "kernels only); use 'fp32' or 'fp32_split3'")
+        if self.world > 1:
+            raise VnetHipError("Networks.Name 'UNet' under data parallelism is not built (world size %d); run it on one device"
+                               % self.world)
 
     def _validate_loss(self):
         """Loss.Name check of model.py:495-560, INCLUDING its fall-through: `if name == "xent"` (model.py:495) is a

@@ -195,3 +195,132 @@ class VNet(object):
                     x = L.batch_normalization(x, activation=activation_fn, residual=r if last else None)
                 x = ops.dropout(x, dropout_rate)
         return x
+
+
+class UNet(object):
+    """Mirror of the reference's `class UNet` (networks.py:4-150), the network model.py:414-427 builds for
+    `Networks.Name == "UNet"`: 3x3x3 SAME convolutions, 2x2x2 VALID max-pooling, 2x2x2 transposed up-convolutions, one batch-norm
+    over each decoder concat.  Same constructor signature / defaults, `GetNetwork(x)`, and TF variable names in creation order
+    ('unet/encoder/level_1/conv_1/weights', ..., 'unet/decoder/level_1/batch_normalization_2/gamma', 'unet/output/...': the
+    decoder block's batch-norms sit OUTSIDE its conv_i scopes, networks.py:65,84).  Differences that do not change results: the
+    concat is never materialised (its batch-norm runs on the two halves, the convolution behind reads two sources) and the
+    activation is fused into the batch-norm kernels.  Batch statistics are always used, like the reference (model.py:747,788,917).
+    ComputeDtype 'fp32' and 'fp32_split3' both run it on the fp32 MFMA kernels (the f32x3 kernels are 5^3 only); 'bf16' is refused."""
+
+    def __init__(self,
+                 num_output_channels,
+                 dropout_rate=0.01,
+                 num_channels=4,
+                 num_levels=4,
+                 num_convolutions=2,
+                 bottom_convolutions=2,
+                 is_training=True,
+                 activation_fn="relu",
+                 device=None):
+        self.num_output_channels = num_output_channels
+        self.dropout_rate = dropout_rate
+        self.num_channels = num_channels
+        self.num_levels = num_levels
+        for what, n in (("num_convolutions", num_convolutions), ("bottom_convolutions", bottom_convolutions)):
+            if isinstance(n, bool) or not isinstance(n, int):
+                raise ValueError("UNet: %s is one integer for every level (reference networks.py:10-11), got %r" % (what, n))
+        self.num_convolutions = num_convolutions
+        self.bottom_convolutions = bottom_convolutions
+        self.is_training = is_training
+        self.train_phase = True            # stand-in for the "train_phase_placeholder" (networks.py:32)
+        if activation_fn not in ("relu", "prelu", "lrelu"):
+            raise ValueError("activation_fn must be relu, prelu or lrelu")
+        self.activation_fn = activation_fn
+        self.fuse_bn_stats = True          # batch-norm statistics from the producing convolution's epilogue (ops.conv bn_stats)
+        self.fuse_grad_accumulation = True # skip features have two consumers: the second gradient is accumulated in place (ops.fork)
+        self.fuse_zero_bias_grad = True    # every conv feeds a batch-norm: its bias gradient is identically 0 (ops.zero_bias_gradients)
+        self.variables = VariableStore(device)
+
+    parameters = VNet.parameters
+    named_parameters = VNet.named_parameters
+    state_dict = VNet.state_dict
+    load_state_dict = VNet.load_state_dict
+    build = VNet.build
+    _dropout_rate = VNet._dropout_rate
+
+    # -- reference networks.py:41-61 -----------------------------------------------------------
+    def convolution_block(self, layer_input, output_channel, num_convolutions, dropout_rate, activation_fn, is_training=True):
+        from . import ops
+        store = self.variables
+        x = layer_input
+        input_channels = L.get_num_channels(x)
+        for i in range(num_convolutions):
+            with store.variable_scope('conv_' + str(i + 1)):
+                x = L.convolution(x, [3, 3, 3, input_channels if i == 0 else output_channel, output_channel], bn_stats=self.fuse_bn_stats)
+                x = L.batch_normalization(x, activation=activation_fn)
+                x = ops.dropout(x, dropout_rate)
+        return x
+
+    # -- reference networks.py:63-99 -----------------------------------------------------------
+    def convolution_block_2(self, layer_input, fine_grained_features, num_convolutions, dropout_rate, activation_fn,
+                            is_training=True):
+        from . import ops
+        store = self.variables
+        num_channels = L.get_num_channels(layer_input)
+        # x = BN(concat(layer_input, features)): per channel, so the two halves are normalised on their own (one variable set)
+        x, skip = L.batch_normalization_concat(layer_input, fine_grained_features)
+        for i in range(num_convolutions):
+            with store.variable_scope('conv_' + str(i + 1)):
+                if i == 0:
+                    x = L.convolution_concat(x, skip, [3, 3, 3, num_channels + L.get_num_channels(skip), num_channels],
+                                             bn_stats=self.fuse_bn_stats)
+                else:
+                    x = L.convolution(x, [3, 3, 3, num_channels, num_channels], bn_stats=self.fuse_bn_stats)
+            x = L.batch_normalization(x, activation=activation_fn)     # (outside the conv_i scope: networks.py:84)
+            x = ops.dropout(x, dropout_rate)
+        return x
+
+    # -- reference networks.py:101-150 ---------------------------------------------------------
+    def GetNetwork(self, x):
+        from . import ops
+        store = self.variables
+        if store.device is None and x.device.type != "meta":
+            store.device = x.device
+        store.begin_pass()
+        dropout_rate = self._dropout_rate()
+        act = self.activation_fn
+        if x.dim() != 5:
+            raise NotImplementedError("only 3-D PatchShape is built (2-D is out of scope, SURVEY section 2 row 11)")
+        if ops.storage_is_bf16() and x.device.type != "meta":
+            raise ops.VnetHipError("ComputeDtype 'bf16' with Networks.Name 'UNet' is not built (the bf16-storage kernels are the "
+                                   "V-Net's 5^3 / 2^3 set); use 'fp32' or 'fp32_split3'")
+        with store.active(), ops.zero_bias_gradients(self.fuse_zero_bias_grad):
+            features = list()
+            for l in range(self.num_levels):
+                with store.variable_scope('unet/encoder/level_' + str(l + 1)):
+                    x = self.convolution_block(x, self.num_channels * (2 ** l), self.num_convolutions, dropout_rate, act)
+                    if self.fuse_grad_accumulation:
+                        skip, x = ops.fork(x)          # skip connection: the decoder's concat batch-norm + the max-pooling consume x
+                        features.append(skip)
+                    else:
+                        features.append(x)
+                    if any(int(v) % 2 for v in x.shape[1:4]):
+                        # VALID pooling floors, the SAME transposed convolution back needs ceil(fine / 2) coarse voxels: TF 1.15
+                        # refuses the reference's graph here (conv3d_transpose: "out_backprop doesn't match computed"), so do we
+                        raise ops.VnetHipError("UNet: level %d has the odd size %s -- every PatchShape axis must be a multiple of "
+                                               "2^NumLevels (the reference's max_pool3d VALID / conv3d_transpose SAME pair does not "
+                                               "build otherwise)" % (l + 1, tuple(int(v) for v in x.shape[1:4])))
+                    with store.variable_scope('max_pooling'):
+                        x = L.max_pool3d(x, ksize=[1, 2, 2, 2, 1], strides=[1, 2, 2, 2, 1], padding='VALID')
+
+            with store.variable_scope('unet/bottom_level'):
+                x = self.convolution_block(x, self.num_channels * (2 ** self.num_levels), self.bottom_convolutions, dropout_rate, act)
+
+            for l in reversed(range(self.num_levels)):
+                with store.variable_scope('unet/decoder/level_' + str(l + 1)):
+                    f = features[l]
+                    with store.variable_scope('up_convolution'):
+                        x = L.up_convolution(x, tuple(f.shape), factor=2, kernel_size=[2, 2, 2])
+                        x = L.batch_normalization(x, activation=act)
+                        x = ops.dropout(x, dropout_rate)
+                    x = self.convolution_block_2(x, f, self.num_convolutions, dropout_rate, act)
+
+            with store.variable_scope('unet/output'):
+                logits = L.convolution(x, [1, 1, 1, self.num_channels, self.num_output_channels])
+                logits = L.batch_normalization(logits)
+        return logits

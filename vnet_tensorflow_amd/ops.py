@@ -1477,6 +1477,111 @@ def bn_update_only(x, C, moving_mean, moving_var):
     _bn_stats(bn_route("stats", M, C, x16=_is16(x), epilogue=pre is not None), x, None, False, M, C, moving_mean, moving_var, pre)
 
 
+# ---- batch-norm over a channel concat (U-Net decoder, reference networks.py:64-65) -------------------------------------------
+# Batch-norm is per channel, so BN(concat(x0, x1)) == concat(BN(x0), BN(x1)) with the matching slices of the ONE variable set
+# gamma / beta / moving_* [C0 + C1]: two ordinary launches per pass, no concat tensor; the convolution behind reads the two results
+# as its two sources.  The parameter gradients land in the matching slices of the variables' gradient (one sink each).
+class _BnConcatFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x0, x1, gamma, beta, mm, mv):
+        L = _lib.lib()
+        ctx.slot1 = getattr(x1, "_vnet_slot", None)
+        x0, x1 = x0.contiguous(), x1.contiguous()
+        M = x0.numel() // x0.shape[-1]
+        ys, saved, ctx.halves, off = [], [], [], 0
+        for x in (x0, x1):
+            C = x.shape[-1]
+            rt = bn_route("act", M, C, x16=_is16(x))
+            sl = slice(off, off + C)
+            mean, invstd, m_total = _bn_stats(rt, x, None, False, M, C, mm[sl] if mm is not None else None,
+                                              mv[sl] if mv is not None else None)
+            y = torch.empty_like(x)
+            name = "vnet_bn_act_fwd" + ("_b16" if rt.apply16 else "")
+            check(getattr(L, name)(_ptr(x), None, 0, M, C, _ptr(mean), _ptr(invstd), _ptr(gamma[sl]), _ptr(beta[sl]), 0, None, _ptr(y),
+                                   _stream()), name)
+            ys.append(y)
+            saved += [x, mean, invstd]
+            ctx.halves.append((rt, sl, M, C, m_total, _SYNC_BN[0] if rt.allreduce else None))
+            off += C
+        ctx.save_for_backward(gamma, beta, *saved)
+        ctx.params = (gamma, beta)
+        return ys[0], ys[1]
+
+    @staticmethod
+    def backward(ctx, dy0, dy1):
+        gamma, beta = ctx.saved_tensors[:2]
+        gref, bref = ctx.params
+        dgamma, sg = _grad_out(gref)
+        dbeta, sbt = _grad_out(bref)
+        out = []
+        for k, (dy, (rt, sl, M, C, m_total, all_reduce)) in enumerate(zip((dy0, dy1), ctx.halves)):
+            x, mean, invstd = ctx.saved_tensors[2 + 3 * k:5 + 3 * k]
+            dy = dy.contiguous()
+            ds = torch.empty_like(dy) if ctx.needs_input_grad[k] else None
+            _bn_backward(rt, dy, x, None, False, M, C, mean, invstd, gamma[sl], beta[sl], 0, None, dgamma[sl], dbeta[sl], None, ds,
+                         m_total, all_reduce)
+            out.append(ds)
+        if out[1] is not None and ctx.slot1 is not None and ctx.slot1.first is None:
+            ctx.slot1.first = out[1]                     # the skip feature's other consumer (the max-pooling) adds its gradient into this
+        return out[0], out[1], _grad_ret(dgamma, sg), _grad_ret(dbeta, sbt), None, None
+
+
+def bn_concat(x0, x1, gamma, beta, moving_mean=None, moving_var=None):
+    """tf.layers.batch_normalization(tf.concat((x0, x1), -1), training=True) (reference networks.py:64-65) as its two halves
+    (y0, y1): gamma / beta / moving_* have C0 + C1 elements."""
+    if gamma.numel() != x0.shape[-1] + x1.shape[-1] or tuple(x0.shape[:-1]) != tuple(x1.shape[:-1]):
+        raise VnetHipError("bn_concat: %s | %s against %d batch-norm channels" % (tuple(x0.shape), tuple(x1.shape), gamma.numel()))
+    if _meta(x0):
+        return torch.empty(x0.shape, device="meta"), torch.empty(x1.shape, device="meta")
+    _need_gpu(x0, "bn_concat")
+    _need_gpu(x1, "bn_concat")
+    return _BnConcatFn.apply(x0, x1, gamma, beta, moving_mean, moving_var)
+
+
+# ---- 2x2x2 stride-2 VALID max-pooling (U-Net encoder, reference networks.py:120; include/vnet_hip_unet.h) --------------------
+class _MaxPool2Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        L = _lib.lib()
+        ctx.slot = getattr(x, "_vnet_slot", None)
+        x = x.contiguous()
+        B, D, H, W, C = x.shape
+        y = torch.empty((B, D // 2, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
+        with _Timed("maxpool2 fwd %d^3x%d %d" % (W, B, C), 0.0, 4.0 * (x.numel() + y.numel())):
+            check(L.vnet_maxpool2_fwd(_ptr(x), _ptr(y), C, B, D, H, W, _stream()), "vnet_maxpool2_fwd")
+        ctx.save_for_backward(x, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _lib.lib()
+        x, y = ctx.saved_tensors
+        dy = dy.contiguous()
+        B, D, H, W, C = x.shape
+        # x's other consumer (the decoder's skip connection) reported its gradient already: add this one into it (ops.fork)
+        acc = _slot_target(ctx.slot, dy, x.shape)
+        dx = acc if acc is not None else torch.empty_like(x)
+        with _Timed("maxpool2 bwd %d^3x%d %d" % (W, B, C), 0.0, 4.0 * (2 * dy.numel() + (3 if acc is not None else 2) * x.numel())):
+            check(L.vnet_maxpool2_bwd(_ptr(dy), _ptr(x), _ptr(y), _ptr(dx), C, B, D, H, W, int(acc is not None), _stream()),
+                  "vnet_maxpool2_bwd")
+        if acc is None and ctx.slot is not None and ctx.slot.first is None:
+            ctx.slot.first = dx
+        return None if acc is not None else dx
+
+
+def max_pool2(x):
+    """tf.nn.max_pool3d(x, [1,2,2,2,1], [1,2,2,2,1], 'VALID') (reference networks.py:120): odd axes floor.  The gradient of a window
+    goes to its first maximum in (z, y, x) scan order."""
+    if x.dim() != 5:
+        raise NotImplementedError("only the 3-D (NDHWC) path is built; 2-D is out of scope (SURVEY section 2 row 11)")
+    if min(int(v) for v in x.shape[1:4]) < 2:
+        raise VnetHipError("max_pool2: every spatial axis must be at least 2, got %s" % (tuple(x.shape[1:4]),))
+    if _meta(x):
+        return torch.empty((x.shape[0],) + tuple(int(v) // 2 for v in x.shape[1:4]) + (x.shape[-1],), device="meta")
+    _need_gpu(x, "max_pool2")
+    return _MaxPool2Fn.apply(x)
+
+
 # ---- stand-alone activation (API parity with layers2.prelu; the networks use the fused bn_act) ------------
 class _ActFn(torch.autograd.Function):
     @staticmethod
