@@ -34,15 +34,16 @@ def _crop_blocks():
     return [(0, 0, 0), (0, 58, 116), (57, 61, 50), (116, 116, 116)]
 
 
-def _oracle_block(xcat, w, z0, y0, x0, rb=None):
-    """Oracle conv output on the 12^3 block at (z0,y0,x0) of a [1,P,P,P,C] tensor (numpy), via a crop with halo."""
-    lo = [max(0, c - 2) for c in (z0, y0, x0)]
-    hi = [min(P, c + 14) for c in (z0, y0, x0)]
+def _oracle_block(xcat, w, z0, y0, x0, rb=None, halo=2, dims=(P, P, P)):
+    """Oracle conv output on the 12^3 block at (z0,y0,x0) of a [B,D,H,W,C] tensor (numpy), via a crop with `halo` voxels around it
+    (2 for the 5^3 filters, 1 for the 3^3 ones)."""
+    lo = [max(0, c - halo) for c in (z0, y0, x0)]
+    hi = [min(n, c + 12 + halo) for n, c in zip(dims, (z0, y0, x0))]
     crop = xcat[:, lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2], :].astype(np.float64)
     if rb is not None:
         crop, w = rb(crop), rb(w)
     y = O.conv_nd_fwd(crop, w.astype(np.float64), 1)
-    # positions whose 5^3 window lies inside the crop or outside the VOLUME (true zero padding) are valid
+    # positions whose window lies inside the crop or outside the VOLUME (true zero padding) are valid
     s = [c - l for c, l in zip((z0, y0, x0), lo)]
     return y[:, s[0]:s[0] + 12, s[1]:s[1] + 12, s[2]:s[2] + 12, :]
 

@@ -65,8 +65,13 @@ def test_conv3_accumulate_is_a_separate_add(dev, shape):
     ((2, 8, 8, 8), 1, 4, False),          # the first layer
 ])
 def test_conv3_epilogue_statistics(dev, shape, Cin, Cout, residual):
+    epilogue_statistics_case(dev, shape, Cin, Cout, residual)
+
+
+def epilogue_statistics_case(dev, shape, Cin, Cout, residual):
     """As test_batch_norm_statistics_from_the_conv_epilogue for the 5^3 kernels, same tolerances: the epilogue's partial sums
-    finalize to the moments of the stored tensor, and the normalised output equals the stream-statistics path's."""
+    finalize to the moments of the stored tensor, and the normalised output equals the stream-statistics path's.  (Also run at the
+    sizes of the 128^3 step by tests/test_hip_unet_fullsize.py.)"""
     from vnet_tensorflow_amd import ops
     gen = torch.Generator().manual_seed(Cin * 7 + Cout)
     B, D, H, W = shape

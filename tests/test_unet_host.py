@@ -237,3 +237,85 @@ def test_unet_config_parses_and_bf16_is_refused_by_name():
         bad = model.image2label(None, _config(name="Dense"), device="cpu", verbose=False)
         bad.read_config()
         bad.build_model_graph()
+
+
+# ---- the full-size fixtures (tests/golden/make_golden_full_unet.py) -------------------------------------------------------------------
+def _full_fixtures():
+    import glob
+    gold = os.path.join(HERE, "golden")
+    return sorted(glob.glob(os.path.join(gold, "unet_*cube*.npz")) + glob.glob(os.path.join(gold, "spread", "unet_*cube*.npz")))
+
+
+def test_full_size_generator_recipe_at_16cube(tmp_path):
+    """make() at a size the CPU suite can afford: the names in creation order, the stored sample positions and a loss equal to
+    O.run_step on the same seeds."""
+    from tests.golden import make_golden_full_unet as G
+    from tests.golden.make_golden_full import SAMPLE, STRIDE, sample_indices
+    case = "u64b2s2"
+    z = np.load(G.make(case, root=str(tmp_path), P=16))
+    fname, _, B, seed = G.CASES[case]
+    net, ps = G.make_net(G.WEIGHT_SEED[case])
+    x, lab = O.synthetic_batch(B, 16, 1, G.CONFIG[0], seed=seed)
+    ref = O.run_step(x.astype(np.float64), lab, net, "sorensen")
+    names = list(ps.vars.keys())
+    assert [str(n) for n in z["names"]] == names == G.creation_order(G.WEIGHT_SEED[case])[0] and len(names) == 100
+    assert float(z["loss"]) == ref["loss"] and z["logits_sample"].dtype == z["grad_sample"].dtype == np.float64
+    assert np.array_equal(z["logits_sample"], ref["logits"][:, ::STRIDE, ::STRIDE, ::STRIDE])
+    for i, n in enumerate(names):
+        gr = ref["grads"][n].ravel()
+        idx = sample_indices(i, gr.size)
+        assert len(idx) == min(gr.size, SAMPLE) and np.array_equal(z["grad_sample"][i][:len(idx)], gr[idx]), n
+        assert z["grad_norm"][i] == np.linalg.norm(gr)
+    assert not os.path.exists(os.path.join(str(tmp_path), G.TF_DIR))          # crops belong to the 128^3 case alone
+    for n, v in ps.state.items():
+        assert np.array_equal(z["state:" + n], v.astype(np.float32))
+
+
+def test_full_size_fixtures_are_well_formed():
+    """Every committed unet_*cube*.npz: the oracle's creation order for the stated configuration, finite arrays, a zero gradient
+    norm for the biases and for nothing else; the teacher-forcing crops of the 128^3 case are all there."""
+    from tests.golden import make_golden_full_unet as G
+    files = _full_fixtures()
+    assert sorted(os.path.relpath(f, os.path.join(HERE, "golden")) for f in files) == sorted(c[0] for c in G.CASES.values())
+    order = G.creation_order()[0]
+    for f in files:
+        z = np.load(f)
+        assert [str(n) for n in z["names"]] == order, f
+        for k in z.files:
+            if k != "names":
+                assert np.isfinite(z[k]).all(), (f, k)
+        for n, gn in zip(order, z["grad_norm"]):
+            assert (gn < 1e-7) == n.endswith("/biases"), (f, n, gn)
+        case = [c for c, v in G.CASES.items() if f.endswith(os.sep + os.path.basename(v[0])) and ("spread" in f) == ("spread" in v[0])][0]
+        assert [int(v) for v in z["config"]] == [G.CASES[case][1], G.CASES[case][2], G.WEIGHT_SEED[case], G.CASES[case][3]]
+    for tag in [t for t, _ in G.TF_LAYERS.values()] + [G.TF_POOL[0]]:
+        x, dy, lo = G.load_tf(tag)
+        assert np.isfinite(x).all() and np.isfinite(dy).all() and np.abs(x).max() > 0 and np.abs(dy).max() > 0
+        assert os.path.getsize(G.tf_path(tag, "x")) < 2 ** 20 and os.path.getsize(G.tf_path(tag, "dy")) < 2 ** 20
+
+
+def test_torch_fp64_reproduces_the_64cube_fixture():
+    """tests/unet_torch.py in float64 shares no code with the generator's oracle; against unet_64cube_b2.npz: logits max-abs 1e-9, loss
+    1e-12, sampled gradient rel-L2 1e-7 per tensor -- about 100 x what the two fp64 implementations differ by on this case (1.8e-11,
+    7.9e-15, 9.5e-10) and five orders below the fp32 figures.  The one place a mistake in the generator would otherwise go unseen."""
+    from tests.golden import make_golden_full_unet as G
+    from tests.golden.make_golden_full import STRIDE, sample_indices
+    from tests.util import rel_l2
+    fname, P, B, seed = G.CASES["u64b2"]
+    z = np.load(os.path.join(HERE, "golden", fname))
+    names, values = G.creation_order(G.WEIGHT_SEED["u64b2"])
+    K, _, C, levels, convs, bottom, _ = G.CONFIG
+    x, lab = O.synthetic_batch(B, P, 1, K, seed=seed)
+    loss, logits, grads = UT.run(values, x.astype(np.float64), lab[..., 0], K, C, levels, convs, bottom, torch.float64)
+    e_logits, e_loss, worst = np.abs(logits[:, ::STRIDE, ::STRIDE, ::STRIDE] - z["logits_sample"]).max(), abs(loss - float(z["loss"])), 0.0
+    compared = 0
+    for i, n in enumerate(names):
+        if n.endswith("/biases"):
+            continue
+        got = grads[n].ravel()
+        idx = sample_indices(i, got.size)
+        worst = max(worst, rel_l2(got[idx], z["grad_sample"][i][:len(idx)]))
+        compared += 1
+    print("torch fp64 against unet_64cube_b2: logits %.2e loss %.2e gradients %.2e (%d tensors)" % (e_logits, e_loss, worst, compared))
+    assert compared == 77
+    assert e_logits < 1e-9 and e_loss < 1e-12 and worst < 1e-7
