@@ -1,4 +1,4 @@
-"""ctypes binding of libvnet_hip.so (include/vnet_hip.h, include/vnet_hip_unet.h).
+"""ctypes binding of libvnet_hip.so (include/vnet_hip.h, include/vnet_hip_unet.h, include/vnet_hip_head.h).
 
 The library is the product: there is NO fallback.  If the shared object is missing, or a
 kernel reports an error, this module raises -- nothing silently routes to PyTorch or the CPU.
@@ -131,6 +131,17 @@ SIGNATURES_UNET = {
     "vnet_maxpool2_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
+# third public header, include/vnet_hip_head.h (the decoder's last batch-norm with the 1x1x1 head folded in), same library
+SIGNATURES_HEAD = {
+    "vnet_bn_head_ok": (_i, [_i, _i]),
+    "vnet_bn_head_stats_rows": (_i, [_i64, _i]),
+    "vnet_bn_head_ws_bytes": (_sz, [_i, _i]),
+    "vnet_bn_act_head_fwd": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "vnet_bn_act_bwd_reduce_head": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vnet_bn_act_bwd_apply_head": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
+}
+
 
 class WgradJob(ctypes.Structure):
     """include/vnet_hip.h: vnet_wgrad_job (one layer of vnet_conv_wgrad_b16_group)."""
@@ -188,9 +199,11 @@ def lib():
                 setattr(L, name, _memo(fn, (b"BF16_DEEP", b"BF16_DEEP_TARGET"), L))     # (the kernel choice follows these options)
             elif name.endswith("_ws_bytes") or name.endswith("_stats_rows") or name == "vnet_conv_stats_from_reduce" or name == "vnet_packed_weight_floats":
                 setattr(L, name, _memo(fn))    # pure size queries, asked before every launch: answer repeats from a dict
-        for name, (res, args) in SIGNATURES_UNET.items():
+        for name, (res, args) in list(SIGNATURES_UNET.items()) + list(SIGNATURES_HEAD.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
+            if name in ("vnet_bn_head_ok", "vnet_bn_head_stats_rows", "vnet_bn_head_ws_bytes"):
+                setattr(L, name, _memo(fn))
         _lib = L
     return _lib
 

@@ -5,6 +5,7 @@
 // its reductions in registers -> wave shuffles -> LDS -> one partial row per workgroup, and a
 // tiny finalize kernel sums the partials in float64 (deterministic, no atomics).
 #include "common.h"
+#include "../../include/vnet_hip_head.h"
 
 namespace {
 
@@ -562,6 +563,14 @@ __global__ void __launch_bounds__(EW_BLOCK) colsum_generic_kernel(const float* _
 }
 
 // ---- 1x1x1 output head (C -> K<=8) ----------------------------------------------------------
+// one channel quad's share of a logit: the head kernel and the fused batch-norm + head kernel both add these shares to the bias
+// in quad order.  Four products and three sums, each rounded on its own (what the compiler made of this line in head_fwd_kernel<2>,
+// where it packs the two classes into v_pk_mul / v_pk_add): contraction is switched off here so that both kernels, and every class
+// count, produce the same bits whatever the vectoriser does around them
+__device__ __forceinline__ float head_quad_dot(const float4 v, float w0, float w1, float w2, float w3) {
+#pragma clang fp contract(off)
+    return v.x * w0 + v.y * w1 + v.z * w2 + v.w * w3;
+}
 template <int K>
 __global__ void __launch_bounds__(EW_BLOCK) head_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ bias, float* __restrict__ y, size_t M, int C) {
@@ -578,8 +587,7 @@ __global__ void __launch_bounds__(EW_BLOCK) head_fwd_kernel(const float* __restr
             for (int c = 0; c < C; c += 4) {
                 const float4 v = *reinterpret_cast<const float4*>(xr + c);
 #pragma unroll
-                for (int k = 0; k < K; ++k)
-                    o[k] += v.x * ws[c * K + k] + v.y * ws[(c + 1) * K + k] + v.z * ws[(c + 2) * K + k] + v.w * ws[(c + 3) * K + k];
+                for (int k = 0; k < K; ++k) o[k] += head_quad_dot(v, ws[c * K + k], ws[(c + 1) * K + k], ws[(c + 2) * K + k], ws[(c + 3) * K + k]);
             }
         } else {
             for (int c = 0; c < C; ++c) {
@@ -669,6 +677,234 @@ __global__ void __launch_bounds__(EW_BLOCK) head_bwd_generic_kernel(const float*
     __syncthreads();
     float* prow = partial + (size_t)blockIdx.x * (C * K + K);
     for (int t = threadIdx.x; t < C * K + K; t += EW_BLOCK) prow[t] = acc[t];
+}
+
+// ---- the decoder's last batch-norm fused with the 1x1x1 head behind it (include/vnet_hip_head.h) --------------------------------
+// C = 4 * CQ channels (CQ = 2 or 4), one thread per (voxel, channel quad) as in the vec kernels above: the CQ lanes of a voxel are
+// neighbours in a wave, a thread keeps its quad on the whole grid-stride walk, so its coefficients and its 4 x K slice of W sit in
+// registers.  Forward: the K logits of a voxel are the bias plus the quads' shares in quad order (head_quad_dot, what
+// head_fwd_kernel adds) -- gathered across the CQ lanes, so y and the logits have head_fwd_kernel's bits; lane 0 of the voxel stores
+// them and keeps their sum / sum of squares for the batch-norm behind the head (one row [sum(K) | sumsq(K)] per workgroup, the
+// layout bn_finalize_kernel reads).  Backward: dy[c] = sum_k W[c][k] dlogits[k] is rebuilt per voxel (head_bwd_kernel's expression)
+// instead of being read from a [M][C] tensor, and the reduce pass also sums dW = y^T dlogits (y rebuilt as the forward computes
+// it) and db.
+struct HeadP {
+    const float* w; const float* bias; const float* dl;     // W [C][K], bias [K] or null, dlogits [M][K]
+    float* logits; float* stats; float* hpartial;           // [M][K]; [grid][2K]; [grid][C*K + K]
+};
+
+template <int K>
+__device__ __forceinline__ void head_load_row(const float* __restrict__ p, size_t row, float (&g)[K]) {
+    if constexpr (K == 2) { const float2 t = reinterpret_cast<const float2*>(p)[row]; g[0] = t.x; g[1] = t.y; }
+    else if constexpr (K == 4) { const float4 t = reinterpret_cast<const float4*>(p)[row]; g[0] = t.x; g[1] = t.y; g[2] = t.z; g[3] = t.w; }
+    else {
+#pragma unroll
+        for (int k = 0; k < K; ++k) g[k] = p[row * K + k];
+    }
+}
+template <int K>
+__device__ __forceinline__ void head_store_row(float* __restrict__ p, size_t row, const float (&g)[K]) {
+    if constexpr (K == 2) reinterpret_cast<float2*>(p)[row] = make_float2(g[0], g[1]);
+    else if constexpr (K == 4) reinterpret_cast<float4*>(p)[row] = make_float4(g[0], g[1], g[2], g[3]);
+    else {
+#pragma unroll
+        for (int k = 0; k < K; ++k) p[row * K + k] = g[k];
+    }
+}
+
+// this thread's quad of the per-channel coefficients and its 4 x K slice of W, from LDS / global into registers
+struct HeadQuad { float sc[4], sf[4], al[4], mu[4], is[4]; };
+template <int K>
+__device__ __forceinline__ void head_quad_load(const BnP& p, const HeadP& h, int c, const float* sc, const float* sf, const float* al,
+                                               HeadQuad& q, float (&wv)[4][K]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        q.sc[i] = sc[c + i]; q.sf[i] = sf[c + i]; q.al[i] = al[c + i];
+        q.mu[i] = p.mean[c + i]; q.is[i] = p.invstd[c + i];
+#pragma unroll
+        for (int k = 0; k < K; ++k) wv[i][k] = h.w[(c + i) * K + k];
+    }
+}
+// dy of this thread's quad from the voxel's dlogits: head_bwd_kernel's expression
+template <int K>
+__device__ __forceinline__ void head_quad_dy(const float (&g)[K], const float (&wv)[4][K], float (&dy)[4]) {
+    float4 o = make_float4(0, 0, 0, 0);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        o.x = fmaf(g[k], wv[0][k], o.x); o.y = fmaf(g[k], wv[1][k], o.y);
+        o.z = fmaf(g[k], wv[2][k], o.z); o.w = fmaf(g[k], wv[3][k], o.w);
+    }
+    dy[0] = o.x; dy[1] = o.y; dy[2] = o.z; dy[3] = o.w;
+}
+
+template <int K, int CQ>
+__global__ void __launch_bounds__(EW_BLOCK) bn_act_head_fwd_kernel(BnP p, HeadP h) {
+    __shared__ float sc[MAXC], sf[MAXC], al[MAXC];
+    bn_load_coef(p, sc, sf, al);
+    const size_t nq = p.M * CQ;
+    const size_t stride = (size_t)gridDim.x * EW_BLOCK;
+    const size_t start = (size_t)blockIdx.x * EW_BLOCK + threadIdx.x;
+    const int cq = (int)(start % CQ), c = cq * 4;       // fixed per thread (grid * 256 % CQ == 0)
+    HeadQuad q; float wv[4][K], bias[K];
+    head_quad_load<K>(p, h, c, sc, sf, al, q, wv);
+#pragma unroll
+    for (int k = 0; k < K; ++k) bias[k] = h.bias ? h.bias[k] : 0.f;
+    float acc[2][8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[0][k] = acc[1][k] = 0.f;
+    for (size_t idx = start; idx < nq; idx += stride) {     // (the CQ lanes of a voxel enter and leave the loop together)
+        float4 v = reinterpret_cast<const float4*>(p.x)[idx];
+        if (p.r) { const float4 t = reinterpret_cast<const float4*>(p.r)[idx]; v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w; }
+        float4 o;
+        o.x = act_fwd(v.x * q.sc[0] + q.sf[0], p.act, q.al[0]);
+        o.y = act_fwd(v.y * q.sc[1] + q.sf[1], p.act, q.al[1]);
+        o.z = act_fwd(v.z * q.sc[2] + q.sf[2], p.act, q.al[2]);
+        o.w = act_fwd(v.w * q.sc[3] + q.sf[3], p.act, q.al[3]);
+        if (p.out) reinterpret_cast<float4*>(p.out)[idx] = o;
+        float part[K], lg[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) { part[k] = head_quad_dot(o, wv[0][k], wv[1][k], wv[2][k], wv[3][k]); lg[k] = bias[k]; }
+#pragma unroll
+        for (int j = 0; j < CQ; ++j)
+#pragma unroll
+            for (int k = 0; k < K; ++k) lg[k] += __shfl(part[k], j, CQ);
+        if (cq == 0) {
+            head_store_row<K>(h.logits, idx / CQ, lg);
+#pragma unroll
+            for (int k = 0; k < K; ++k) { acc[0][k] += lg[k]; acc[1][k] += lg[k] * lg[k]; }
+        }
+    }
+    if (h.stats) block_reduce_row<2, 8>(acc, K, h.stats + (size_t)blockIdx.x * 2 * K);
+}
+
+template <int K, int CQ>
+__global__ void __launch_bounds__(EW_BLOCK) bn_act_bwd_reduce_head_kernel(BnP p, HeadP h) {
+    __shared__ float sc[MAXC], sf[MAXC], al[MAXC];
+    __shared__ float shh[5 * K][EW_BLOCK];
+    bn_load_coef(p, sc, sf, al);
+    constexpr int C = 4 * CQ;
+    const size_t nq = p.M * CQ;
+    const size_t stride = (size_t)gridDim.x * EW_BLOCK;
+    const size_t start = (size_t)blockIdx.x * EW_BLOCK + threadIdx.x;
+    const int cq = (int)(start % CQ), c = cq * 4;
+    HeadQuad q; float wv[4][K];
+    head_quad_load<K>(p, h, c, sc, sf, al, q, wv);
+    float4 acc[3] = {make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};
+    float hs[5 * K];                               // dW of the quad's 4 channels [4][K], then db [K] (lane 0 of the voxel only)
+#pragma unroll
+    for (int s = 0; s < 5 * K; ++s) hs[s] = 0.f;
+    constexpr int U = VNET_BN_RED_U;
+    for (size_t idx = start; idx < nq; idx += U * stride) {
+        float4 v[U]; float g[U][K];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const size_t j0 = idx + u * stride;
+            const bool ok = j0 < nq;
+            const size_t j = ok ? j0 : idx;
+            v[u] = reinterpret_cast<const float4*>(p.x)[j];
+            if (p.r) { const float4 t = reinterpret_cast<const float4*>(p.r)[j]; v[u].x += t.x; v[u].y += t.y; v[u].z += t.z; v[u].w += t.w; }
+            head_load_row<K>(h.dl, j / CQ, g[u]);
+            if (!ok) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) g[u][k] = 0.f;     // dlogits = 0 contributes nothing to any sum
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float vv[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+            float gg[4], a0[4], a1[4], a2[4];
+            head_quad_dy<K>(g[u], wv, gg);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float z = vv[i] * q.sc[i] + q.sf[i];
+                const float dz = gg[i] * act_grad(z, p.act, q.al[i]);
+                const float xh = (vv[i] - q.mu[i]) * q.is[i];
+                a0[i] = dz; a1[i] = dz * xh; a2[i] = gg[i] * fminf(z, 0.f);
+                const float y = act_fwd(z, p.act, q.al[i]);
+#pragma unroll
+                for (int k = 0; k < K; ++k) hs[i * K + k] = fmaf(y, g[u][k], hs[i * K + k]);
+            }
+            acc[0].x += a0[0]; acc[0].y += a0[1]; acc[0].z += a0[2]; acc[0].w += a0[3];
+            acc[1].x += a1[0]; acc[1].y += a1[1]; acc[1].z += a1[2]; acc[1].w += a1[3];
+            acc[2].x += a2[0]; acc[2].y += a2[1]; acc[2].z += a2[2]; acc[2].w += a2[3];
+            if (cq == 0) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) hs[4 * K + k] += g[u][k];
+            }
+        }
+    }
+    block_reduce_vec<3>(acc, CQ, C, p.partial + (size_t)blockIdx.x * 3 * C);
+    // the head's sums meet in the order of head_bwd_kernel's LDS tree (thread t with t + 128, those with t + 64, then the lanes 32,
+    // 16, ... CQ apart), so dw / db have that kernel's bits: db is analytically 0 when a batch-norm follows the head, what is left of
+    // it is round-off that an optimiser which normalises gradients (Adam) turns into a full-size step
+#pragma unroll
+    for (int s = 0; s < 5 * K; ++s) shh[s][threadIdx.x] = hs[s];
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const int t = threadIdx.x;
+        float* prow = h.hpartial + (size_t)blockIdx.x * (C * K + K);
+#pragma unroll
+        for (int s = 0; s < 5 * K; ++s) {
+            float v = (shh[s][t] + shh[s][t + 128]) + (shh[s][t + 64] + shh[s][t + 192]);
+#pragma unroll
+            for (int o = 32; o >= CQ; o >>= 1) v += __shfl_down(v, o, 64);
+            if (s < 4 * K) { if (t < CQ) prow[(t * 4 + s / K) * K + s % K] = v; }
+            else if (t == 0) prow[C * K + s - 4 * K] = v;
+        }
+    }
+}
+
+template <int K, int CQ>
+__global__ void __launch_bounds__(EW_BLOCK) bn_act_bwd_apply_head_kernel(BnP p, HeadP h) {
+    __shared__ float sc[MAXC], sf[MAXC], al[MAXC];
+    bn_load_coef(p, sc, sf, al);
+    const size_t nq = p.M * CQ;
+    const size_t stride = (size_t)gridDim.x * EW_BLOCK;
+    const size_t start = (size_t)blockIdx.x * EW_BLOCK + threadIdx.x;
+    const int cq = (int)(start % CQ), c = cq * 4;
+    HeadQuad q; float wv[4][K], k1[4], k2[4], ex[4];
+    head_quad_load<K>(p, h, c, sc, sf, al, q, wv);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        k1[i] = p.dbeta[c + i] * p.invM; k2[i] = p.dgamma[c + i] * p.invM;
+        ex[i] = p.extra ? p.extra[c + i] : 0.f;
+    }
+    for (size_t idx = start; idx < nq; idx += stride) {
+        float4 v = reinterpret_cast<const float4*>(p.x)[idx];
+        if (p.r) { const float4 t = reinterpret_cast<const float4*>(p.r)[idx]; v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w; }
+        float g[K], gg[4], o[4];
+        head_load_row<K>(h.dl, idx / CQ, g);
+        head_quad_dy<K>(g, wv, gg);
+        const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float z = vv[i] * q.sc[i] + q.sf[i];
+            const float dz = gg[i] * act_grad(z, p.act, q.al[i]);
+            const float xh = (vv[i] - q.mu[i]) * q.is[i];
+            o[i] = q.sc[i] * (dz - k1[i] - xh * k2[i]) + xh * ex[i];
+        }
+        reinterpret_cast<float4*>(p.out)[idx] = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+// the two finalizes of the fused backward in one launch: workgroups [0, C) sum the batch-norm's three columns
+// (sum_finalize_kernel), workgroups [C, C + CK + K) one column of dW / db each (head_finalize_kernel)
+__global__ void __launch_bounds__(256) bn_head_finalize_kernel(const float* __restrict__ bnp, const float* __restrict__ hp, int nblk,
+                                                               int C, int CK, int K, float* o0, float* o1, float* o2, float* dw, float* db) {
+    if ((int)blockIdx.x < C) {
+        const int c = blockIdx.x;
+        double s[3];
+        block_colsum_multi<3>(bnp, nblk, (size_t)3 * C, c, C, s);
+        if (threadIdx.x == 0) {
+            if (o0) o0[c] = (float)s[0];
+            if (o1) o1[c] = (float)s[1];
+            if (o2) o2[c] = (float)s[2];
+        }
+        return;
+    }
+    const int c = blockIdx.x - C;
+    const double s = block_colsum_d(hp, nblk, (size_t)(CK + K), c);
+    if (threadIdx.x == 0) { if (c < CK) dw[c] = (float)s; else db[c - CK] = (float)s; }
 }
 
 // ---- fused softmax + Dice / cross-entropy ------------------------------------------------------
@@ -1653,6 +1889,11 @@ __global__ void dropout_bwd_b16_kernel(const u32x4* __restrict__ dy, const uint8
 // the class count K (1..8) as a template argument
 template <typename F>
 static int with_k(int K, F&& f) { return with_int<1, 2, 3, 4, 5, 6, 7, 8>(K, f); }
+// the class count K and the channel-quad count CQ = C / 4 (2 or 4) of the fused batch-norm + head kernels as template arguments
+template <typename F>
+static int with_k_cq(int K, int C, F&& f) {
+    return with_k(K, [&](auto KK) { return with_int<2, 4>(C / 4, [&](auto CQ) { return f(KK, CQ); }); });
+}
 // the (BCAST, HASR) instantiations of the bf16 batch-norm kernels: broadcast statistics never come with a residual
 template <typename F>
 static int with_bcast_r(bool bcast, bool hasr, F&& f) {
@@ -1900,6 +2141,66 @@ int vnet_head_bwd(const float* x, const float* w, const float* dy, float* dx, fl
     }
     if (e) return e;
     return launch<head_finalize_kernel>(dim3(C * K + K), dim3(256), 0, st, partial, nblk, C * K, K, dw, db);
+}
+
+// ---- include/vnet_hip_head.h: the decoder's last batch-norm with the head folded in ----
+static inline bool bn_head_shape_ok(int C, int K) { return (C == 8 || C == 16) && K >= 1 && K <= 8; }
+static inline int bn_head_blocks(int64_t M, int C) { return ew_blocks((size_t)M * C / 4 / 4 + 1); }
+
+int vnet_bn_head_ok(int C, int K) { return bn_head_shape_ok(C, K) ? 1 : 0; }
+int vnet_bn_head_stats_rows(int64_t M, int C) { return (M > 0 && (C == 8 || C == 16)) ? bn_head_blocks(M, C) : 0; }
+size_t vnet_bn_head_ws_bytes(int C, int K) { return (size_t)EW_MAXBLK * (3 * C + C * K + K) * sizeof(float); }
+
+int vnet_bn_act_head_fwd(const float* x, const float* r, int64_t M, int C,
+                         const float* mean, const float* invstd, const float* gamma, const float* beta, int act, const float* alpha,
+                         const float* w, const float* bias, int K, float* y, float* logits, float* stats, void* stream) {
+    if (!x || !mean || !invstd || !gamma || !beta || !w || !logits || M <= 0) return VNET_E_BADARG;
+    if (act == VNET_ACT_PRELU && !alpha) return VNET_E_BADARG;
+    if (act < 0 || act > 3 || !bn_head_shape_ok(C, K)) return VNET_E_UNSUPPORTED;
+    BnP p{}; p.x = x; p.r = r; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta; p.alpha = alpha;
+    p.out = y; p.M = (size_t)M; p.C = C; p.act = act;
+    HeadP h{}; h.w = w; h.bias = bias; h.logits = logits; h.stats = stats;
+    return with_k_cq(K, C, [&](auto KK, auto CQ) {
+        return launch<bn_act_head_fwd_kernel<KK, CQ>>(dim3(bn_head_blocks(M, C)), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, h);
+    });
+}
+
+int vnet_bn_act_bwd_reduce_head(const float* dlogits, const float* w, int K, const float* x, const float* r, int64_t M, int C,
+                                const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                int act, const float* alpha, float* dgamma, float* dbeta, float* dalpha, float* dw, float* db,
+                                void* ws, size_t ws_bytes, void* stream) {
+    if (!dlogits || !w || !x || !mean || !invstd || !gamma || !beta || !dgamma || !dbeta || !dw || !db || M <= 0) return VNET_E_BADARG;
+    if (act == VNET_ACT_PRELU && (!alpha || !dalpha)) return VNET_E_BADARG;
+    if (act < 0 || act > 3 || !bn_head_shape_ok(C, K)) return VNET_E_UNSUPPORTED;
+    if (!ws || ws_bytes < vnet_bn_head_ws_bytes(C, K)) return VNET_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    BnP p{}; bn_bwd_fill(p, nullptr, x, r, 0, M, C, mean, invstd, gamma, beta, act, alpha);
+    p.partial = (float*)ws;
+    HeadP h{}; h.w = w; h.dl = dlogits; h.hpartial = p.partial + (size_t)EW_MAXBLK * 3 * C;
+    const int nblk = bn_head_blocks(M, C);
+    if (int e = with_k_cq(K, C, [&](auto KK, auto CQ) {
+            return launch<bn_act_bwd_reduce_head_kernel<KK, CQ>>(dim3(nblk), dim3(EW_BLOCK), 0, st, p, h); }))
+        return e;
+    return launch<bn_head_finalize_kernel>(dim3(C + C * K + K), dim3(256), 0, st, (const float*)p.partial, (const float*)h.hpartial, nblk,
+                                           C, C * K, K, dbeta, dgamma, act == VNET_ACT_PRELU ? dalpha : (float*)nullptr, dw, db);
+}
+
+int vnet_bn_act_bwd_apply_head(const float* dlogits, const float* w, int K, const float* x, const float* r, int64_t M, int C,
+                               const float* mean, const float* invstd, const float* gamma, const float* beta,
+                               int act, const float* alpha, const float* sum_dz, const float* sum_dz_xhat, double M_total,
+                               const float* xhat_coef, float* ds, void* stream) {
+    if (!dlogits || !w || !x || !mean || !invstd || !gamma || !beta || !sum_dz || !sum_dz_xhat || !ds || M <= 0 || M_total <= 0.0)
+        return VNET_E_BADARG;
+    if (act == VNET_ACT_PRELU && !alpha) return VNET_E_BADARG;
+    if (act < 0 || act > 3 || !bn_head_shape_ok(C, K)) return VNET_E_UNSUPPORTED;
+    BnP p{}; bn_bwd_fill(p, nullptr, x, r, 0, M, C, mean, invstd, gamma, beta, act, alpha);
+    p.invM = (float)(1.0 / M_total);
+    p.extra = xhat_coef;
+    p.out = ds; p.dgamma = sum_dz_xhat; p.dbeta = sum_dz;
+    HeadP h{}; h.w = w; h.dl = dlogits;
+    return with_k_cq(K, C, [&](auto KK, auto CQ) {
+        return launch<bn_act_bwd_apply_head_kernel<KK, CQ>>(dim3(bn_head_blocks(M, C)), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, h);
+    });
 }
 
 int vnet_softmax_dice_fwd(const float* logits, const int32_t* labels, int B, int64_t V, int K,

@@ -169,8 +169,29 @@ def convolution_tiled(tiled, filter, bn_stats=False, bn_residual=None):
     return ops.input_conv(img, gamma, beta, mean, invstd, w, b, bn_stats=bn_stats, bn_residual=bn_residual)
 
 
+class DeferredNorm(object):
+    """A batch_normalization() / batch_normalization_chain() whose variables exist and whose kernels have not run yet: the layer
+    behind it is the 1x1x1 output convolution, which convolution_after_norm() folds into the same passes (ops.bn_head).
+    kind -1: layers = [(gamma, beta, mm, mv)] of batch_normalization(x, activation, residual); kind 0 / 1: the chain's layers."""
+
+    def __init__(self, x, kind, activation, alpha, layers, residual=None):
+        self.x, self.kind, self.activation, self.alpha, self.layers, self.residual = x, kind, activation, alpha, layers, residual
+        self.shape = x.shape
+
+
+def convolution_after_norm(d, filter):
+    """convolution(y, [1, 1, 1, C, K]) for the y of the deferred batch-norm (chain) `d`: the same variables ('weights', 'biases')."""
+    filter = list(filter)
+    assert filter[:3] == [1, 1, 1], filter
+    w = get_variable(name='weights', initializer=lambda: xavier_initializer_convolution(shape=filter))
+    b = get_variable(name='biases', initializer=lambda: constant_initializer(0, shape=filter[-1]))
+    g = [v for layer in d.layers for v in layer[:2]] + [None] * (6 - 2 * len(d.layers))
+    moving = [v for layer in d.layers for v in layer[2:]] + [None] * (6 - 2 * len(d.layers))
+    return ops.bn_head(d.x, w, b, d.kind, d.activation, d.alpha, *g, residual=d.residual, moving=tuple(moving))
+
+
 def batch_normalization(x, activation=None, residual=None, tile=False, channels=None, dead=False,
-                        momentum=0.99, epsilon=0.001, want_stats=False):
+                        momentum=0.99, epsilon=0.001, want_stats=False, defer=False):
     """tf.layers.batch_normalization(x, momentum=0.99, epsilon=0.001, center=True, scale=True,
     training=True) -- the reference feeds train_phase=True everywhere (model.py:747,788,917) --
     fused with the optional residual add in front (x + residual), the tf.tile of a 1-channel
@@ -184,6 +205,9 @@ def batch_normalization(x, activation=None, residual=None, tile=False, channels=
     alpha = None
     if activation == "prelu":
         alpha = get_variable('alpha', initializer=lambda: np.full((C,), 0.1, dtype=np.float32))
+    if defer:
+        assert not tile and not want_stats
+        return DeferredNorm(x, -1, activation, alpha, [(gamma, beta, mm, mv)], residual)
     if want_stats:
         y, mean, invstd = ops.bn_act(x, gamma, beta, activation, alpha, residual, tile, mm, mv, want_stats=True)
         return y, (x, gamma, beta, mean, invstd)
@@ -201,15 +225,18 @@ def _bn_variables(C):
     return gamma, beta, mm, mv
 
 
-def batch_normalization_chain(x, kind, activation=None):
+def batch_normalization_chain(x, kind, activation=None, defer=False):
     """The decoder's batch-norm chains (reference networks.py:333-337 / 358-361), each evaluated as ONE fused
     normalisation of x (see ops.bn_chain): same variables, created in the reference's order and under its names,
-        kind 0:  x = BN(x); r = BN(x); x = act(BN(x + r))          kind 1:  r = BN(x); x = act(BN(x + r))."""
+        kind 0:  x = BN(x); r = BN(x); x = act(BN(x + r))          kind 1:  r = BN(x); x = act(BN(x + r)).
+    defer: create the variables only and return a DeferredNorm (batch_normalization(defer=True) likewise)."""
     C = int(x.shape[-1])
     layers = [_bn_variables(C) for _ in range(3 if kind == 0 else 2)]
     alpha = None
     if activation == "prelu":
         alpha = get_variable('alpha', initializer=lambda: np.full((C,), 0.1, dtype=np.float32))
+    if defer:
+        return DeferredNorm(x, kind, activation, alpha, layers)
     (g1, b1, mm1, mv1), (g2, b2, mm2, mv2) = layers[0], layers[1]
     g3 = b3 = mm3 = mv3 = None
     if kind == 0:

@@ -46,6 +46,7 @@ class VNet(object):
         self.fuse_bn_stats = True          # batch-norm statistics from the producing convolution's epilogue (ops.conv bn_stats)
         self.fuse_grad_accumulation = True # tensors with two consumers: second gradient accumulated by its producer (ops.fork)
         self.fuse_zero_bias_grad = True    # conv biases feed batch-norms: their gradient is identically 0 (ops.zero_bias_gradients)
+        self.fuse_head = True              # the 1x1x1 output convolution runs inside the decoder's last batch-norm passes (ops.bn_head)
         self.variables = VariableStore(device)
 
     # -- torch.nn.Module-like conveniences -------------------------------------------------
@@ -132,10 +133,15 @@ class VNet(object):
                     with store.variable_scope('up_convolution'):
                         x = L.up_convolution(x, tuple(f.shape), factor=2, kernel_size=[2, 2, 2])
                         x = L.batch_normalization(x, activation=act)
-                    x = self.convolution_block_2(x, f, self.num_convolutions[l], dropout_rate, act)
+                    x = self.convolution_block_2(x, f, self.num_convolutions[l], dropout_rate, act,
+                                                 head=(l == 0 and self.fuse_head))
 
             with store.variable_scope('vnet/output_layer'):
-                logits = L.convolution(x, [1, 1, 1, self.num_channels, self.num_classes])
+                if isinstance(x, L.DeferredNorm):
+                    # the block's last batch-norm has not run: it and the 1x1x1 convolution share their passes
+                    logits = L.convolution_after_norm(x, [1, 1, 1, self.num_channels, self.num_classes])
+                else:
+                    logits = L.convolution(x, [1, 1, 1, self.num_channels, self.num_classes])
                 logits = L.batch_normalization(logits)
         return logits
 
@@ -161,21 +167,25 @@ class VNet(object):
 
     # -- reference networks.py:324-365 ---------------------------------------------------------
     def convolution_block_2(self, layer_input, fine_grained_features, num_convolutions, dropout_rate, activation_fn,
-                            is_training=True):
+                            is_training=True, head=False):
+        """head: the block's output feeds only the 1x1x1 output convolution -- with no dropout in between its last batch-norm is
+        returned un-run (layers2.DeferredNorm) for the output layer to fold the convolution into."""
         from . import ops
         store = self.variables
         n_channels = L.get_num_channels(layer_input)
+        defer = bool(head) and dropout_rate == 0.0
         if num_convolutions == 1:
             with store.variable_scope('conv_' + str(1)):
                 x = L.convolution_concat(layer_input, fine_grained_features, [5, 5, 5, n_channels * 2, n_channels], bn_stats=self.fuse_bn_stats)
                 if self.fuse_bn_chains:
                     # x = BN(x); r = BN(x) (networks.py:335); x = act(BN(x + r)) -- one fused normalisation of the conv output
-                    x = L.batch_normalization_chain(x, 0, activation_fn)
+                    x = L.batch_normalization_chain(x, 0, activation_fn, defer=defer)
                 else:
                     x = L.batch_normalization(x)
                     r = L.batch_normalization(x)                                       # networks.py:335
-                    x = L.batch_normalization(x, activation=activation_fn, residual=r)  # x = x + layer_input ; BN ; act
-                x = ops.dropout(x, dropout_rate)
+                    x = L.batch_normalization(x, activation=activation_fn, residual=r, defer=defer)  # x = x + layer_input ; BN ; act
+                if not defer:
+                    x = ops.dropout(x, dropout_rate)
             return x
 
         with store.variable_scope('conv_' + str(1)):
@@ -189,11 +199,12 @@ class VNet(object):
                 last = (i == num_convolutions - 1)
                 # networks.py:358 builds this BN for every i; its output is used only by the last conv
                 if last and self.fuse_bn_chains:
-                    x = L.batch_normalization_chain(x, 1, activation_fn)               # r = BN(x); x = act(BN(x + r))
+                    x = L.batch_normalization_chain(x, 1, activation_fn, defer=defer)  # r = BN(x); x = act(BN(x + r))
                 else:
                     r = L.batch_normalization(x, dead=not last)
-                    x = L.batch_normalization(x, activation=activation_fn, residual=r if last else None)
-                x = ops.dropout(x, dropout_rate)
+                    x = L.batch_normalization(x, activation=activation_fn, residual=r if last else None, defer=defer and last)
+                if not (defer and last):
+                    x = ops.dropout(x, dropout_rate)
         return x
 
 

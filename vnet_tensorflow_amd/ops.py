@@ -1283,21 +1283,33 @@ def _bn_stats(rt, x, r, bcast, M, C, mm, mv, pre=None):
 
 
 def _bn_backward(rt, dy, x, r, bcast, M, C, mean, invstd, scale, shift, act, alpha, dscale, dshift, dalpha, ds, m_total,
-                 all_reduce=None, coef=None):
+                 all_reduce=None, coef=None, head=None):
     """Backward of y = act(scale * xhat + shift), xhat the normalised s = x (+ r): the sums sum_dz_xhat -> dscale, sum_dz -> dshift
     (and dalpha), all-reduced when rt says so, then ds (None: no data gradient) from them.  coef(sum_dz_xhat) runs between the two
-    and returns the apply's xhat coefficient (the chain's vnet_bn_chain_coef_bwd)."""
+    and returns the apply's xhat coefficient (the chain's vnet_bn_chain_coef_bwd).
+    head = (w, dw, db): y feeds the 1x1x1 head y W + b and `dy` is the gradient of its LOGITS -- both passes form dy = dlogits W^T
+    per voxel and the first one also sums the head's dw / db (include/vnet_hip_head.h; float32, rt.stats not "small")."""
     L = _lib.lib()
-    nb = L.vnet_bn_ws_bytes(C)
-    ws = workspace(nb, dy.device)
-    if rt.stats == "small":
-        check(L.vnet_bn_small_bwd_b16(_ptr(dy), _ptr(x), _ptr(r), M, C, _ptr(mean), _ptr(invstd), _ptr(scale), _ptr(shift), act,
-                                      _ptr(alpha), _ptr(dscale), _ptr(dshift), _ptr(dalpha), _ptr(ds), _stream()), "vnet_bn_small_bwd_b16")
-        return
-    sfx = "_b16" if rt.apply16 else ""
-    args = (_ptr(dy), _ptr(x), _ptr(r), int(bcast), M, C, _ptr(mean), _ptr(invstd), _ptr(scale), _ptr(shift), act, _ptr(alpha))
-    name = "vnet_bn_act_bwd_reduce" + sfx
-    check(getattr(L, name)(*args, _ptr(dscale), _ptr(dshift), _ptr(dalpha), _ptr(ws), nb, _stream()), name)
+    if head is not None:
+        w, dw, db = head
+        K = int(w.shape[-1])
+        nb = L.vnet_bn_head_ws_bytes(C, K)
+        ws = workspace(nb, dy.device)
+        sfx = "_head"
+        args = (_ptr(dy), _ptr(w), K, _ptr(x), _ptr(r), M, C, _ptr(mean), _ptr(invstd), _ptr(scale), _ptr(shift), act, _ptr(alpha))
+        check(L.vnet_bn_act_bwd_reduce_head(*args, _ptr(dscale), _ptr(dshift), _ptr(dalpha), _ptr(dw), _ptr(db), _ptr(ws), nb, _stream()),
+              "vnet_bn_act_bwd_reduce_head")
+    else:
+        nb = L.vnet_bn_ws_bytes(C)
+        ws = workspace(nb, dy.device)
+        if rt.stats == "small":
+            check(L.vnet_bn_small_bwd_b16(_ptr(dy), _ptr(x), _ptr(r), M, C, _ptr(mean), _ptr(invstd), _ptr(scale), _ptr(shift), act,
+                                          _ptr(alpha), _ptr(dscale), _ptr(dshift), _ptr(dalpha), _ptr(ds), _stream()), "vnet_bn_small_bwd_b16")
+            return
+        sfx = "_b16" if rt.apply16 else ""
+        args = (_ptr(dy), _ptr(x), _ptr(r), int(bcast), M, C, _ptr(mean), _ptr(invstd), _ptr(scale), _ptr(shift), act, _ptr(alpha))
+        name = "vnet_bn_act_bwd_reduce" + sfx
+        check(getattr(L, name)(*args, _ptr(dscale), _ptr(dshift), _ptr(dalpha), _ptr(ws), nb, _stream()), name)
     sdz, sdzx = dshift, dscale
     if rt.allreduce and (ds is not None or coef is not None):
         # this replica's parameter gradients stay local (the gradient all-reduce averages them); the data gradient needs the sums
@@ -1667,6 +1679,130 @@ def head_conv(x, w, b):
 
 
 # ---- fused softmax + Dice / cross-entropy loss ---------------------------------------------------------------
+# ---- the decoder's last batch-norm with the head folded in (include/vnet_hip_head.h) ---------------------------------------------
+# "stats": the normalise pass also writes the statistics rows of the logits, so the batch-norm behind the head runs only its finalize
+# (12 us and a launch at 128^3).  Off: those rows group the voxels differently from vnet_bn_stats, mean / invstd move in the last
+# bit, and with them the round-off that is all there is of the head bias's gradient (analytically 0 in front of a batch-norm) --
+# which Adam turns into full-size steps of that parameter.  Without it the fused step computes the unfused step's bits.
+_HEAD_FUSE = {"on": True, "stats": False}
+
+
+def set_head_fusion(on, stats=None):
+    """on=False: bn_head() runs the unfused sequence (bn_chain / bn_act, then head_conv); stats (None: unchanged): the fused
+    normalise pass also produces the logits' batch-norm partial sums.  Returns the previous (on, stats)."""
+    prev = (_HEAD_FUSE["on"], _HEAD_FUSE["stats"])
+    _HEAD_FUSE["on"] = bool(on)
+    if stats is not None:
+        _HEAD_FUSE["stats"] = bool(stats)
+    return prev
+
+
+class _BnHeadFn(torch.autograd.Function):
+    """logits = head_conv(y), y the output of bn_chain(x, kind, ...) (kind 0 / 1) or of bn_act(x, g1, b1, act, alpha, residual=r)
+    (kind -1), in one normalise pass that also writes the partial sums of the logits into `stats` (None: not) for the batch-norm
+    behind the head.  y is not stored: nothing but the head reads it, and the backward rebuilds it from x.  Backward: one reduce and one apply
+    pass read dlogits (K floats per voxel) in place of a [M][C] gradient of y; the reduce also sums the head's dw / db."""
+
+    @staticmethod
+    def forward(ctx, x, r, kind, act, alpha, w, b, stats, bufs, g1, b1, g2, b2, g3, b3):
+        L = _lib.lib()
+        C, K = int(w.shape[-2]), int(w.shape[-1])
+        pre = _epilogue_of(x, r, C)
+        x = x.contiguous()
+        r = r.contiguous() if r is not None else None
+        M = x.numel() // C
+        dev = x.device
+        mm1, mv1, mm2, mv2, mm3, mv3 = bufs
+        if kind < 0:
+            ctx.rt = rt = bn_route("act", M, C, False, False, None if r is None else False, pre is not None)
+        else:
+            ctx.rt = rt = bn_route("chain", M, C, x16=False, epilogue=pre is not None)
+        mean, invstd, ctx.m_total = _bn_stats(rt, x, r, False, M, C, mm1, mv1, pre)
+        ctx.all_reduce = _SYNC_BN[0] if rt.allreduce else None
+        scale, shift = g1, b1
+        if kind >= 0:
+            scale = torch.empty(C, dtype=torch.float32, device=dev)
+            shift = torch.empty(C, dtype=torch.float32, device=dev)
+            check(L.vnet_bn_chain_coef_fwd(kind, C, BN_EPS, BN_MOMENTUM, _ptr(mean), _ptr(invstd), _ptr(g1), _ptr(b1), _ptr(g2), _ptr(b2),
+                                           _ptr(g3), _ptr(b3), _ptr(scale), _ptr(shift), _ptr(mm2), _ptr(mv2), _ptr(mm3), _ptr(mv3),
+                                           _stream()), "vnet_bn_chain_coef_fwd")
+        logits = torch.empty(x.shape[:-1] + (K,), dtype=torch.float32, device=dev)
+        check(L.vnet_bn_act_head_fwd(_ptr(x), _ptr(r), M, C, _ptr(mean), _ptr(invstd), _ptr(scale), _ptr(shift), act, _ptr(alpha),
+                                     _ptr(w), _ptr(b), K, None, _ptr(logits), _ptr(stats), _stream()), "vnet_bn_act_head_fwd")
+        ctx.save_for_backward(x, r, alpha, w, g1, g2, g3, mean, invstd, scale, shift)
+        ctx.params = (alpha, w, b, g1, b1, g2, b2, g3, b3)
+        ctx.cfg = (kind, act, M, C)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dl):
+        L = _lib.lib()
+        x, r, alpha, w, g1, g2, g3, mean, invstd, scale, shift = ctx.saved_tensors
+        kind, act, M, C = ctx.cfg
+        aref, wref, bref, g1r, b1r, g2r, b2r, g3r, b3r = ctx.params
+        dl = dl.contiguous()
+        dev = dl.device
+        dw, sw = _grad_out(wref)
+        db, sb = _grad_out(bref)
+        dalpha, sa = _grad_out(aref) if alpha is not None else (None, None)
+        need_ds = ctx.needs_input_grad[0] or (r is not None and ctx.needs_input_grad[1])
+        ds = torch.empty(x.shape, dtype=torch.float32, device=dev) if need_ds else None
+        outs = [_grad_out(p) if p is not None else (None, None) for p in (g1r, b1r, g2r, b2r, g3r, b3r)]
+        (dg1, s1), (db1, t1), (dg2, s2), (db2, t2), (dg3, s3), (db3, t3) = outs
+        if kind < 0:
+            _bn_backward(ctx.rt, dl, x, r, False, M, C, mean, invstd, scale, shift, act, alpha, dg1, db1, dalpha, ds, ctx.m_total,
+                         ctx.all_reduce, head=(w, dw, db))
+        else:
+            dC = torch.empty(C, dtype=torch.float32, device=dev)
+            dD = torch.empty(C, dtype=torch.float32, device=dev)
+            extra = torch.empty(C, dtype=torch.float32, device=dev)
+
+            def coef(dCg):        # every gamma / beta gradient of the chain, and the xhat coefficient of the apply
+                check(L.vnet_bn_chain_coef_bwd(kind, C, BN_EPS, ctx.m_total, _ptr(mean), _ptr(invstd), _ptr(g1), _ptr(g2), _ptr(g3),
+                                               _ptr(dC), _ptr(dD), _ptr(dCg), _ptr(dg1), _ptr(db1), _ptr(dg2), _ptr(db2), _ptr(dg3),
+                                               _ptr(db3), _ptr(extra), _stream()), "vnet_bn_chain_coef_bwd")
+                return extra
+            _bn_backward(ctx.rt, dl, x, None, False, M, C, mean, invstd, scale, shift, act, alpha, dC, dD, dalpha, ds, ctx.m_total,
+                         ctx.all_reduce, coef, head=(w, dw, db))
+        ret = [_grad_ret(g, s_) if p is not None else None
+               for g, s_, p in ((dg1, s1, g1r), (db1, t1, b1r), (dg2, s2, g2r), (db2, t2, b2r), (dg3, s3, g3r), (db3, t3, b3r))]
+        return (ds, (ds if r is not None else None), None, None, _grad_ret(dalpha, sa) if alpha is not None else None,
+                _grad_ret(dw, sw), _grad_ret(db, sb), None, None) + tuple(ret)
+
+
+def bn_head(x, w, b, kind, act, alpha, g1, b1, g2=None, b2=None, g3=None, b3=None, residual=None, moving=(None,) * 6):
+    """head_conv(y, w, b) of y = bn_chain(x, kind, act, alpha, g1, b1, g2, b2, g3, b3, moving) (kind 0 / 1) or of
+    y = bn_act(x, g1, b1, act, alpha, residual, moving_mean=moving[0], moving_var=moving[1]) (kind -1), for a y nothing else reads.
+    float32 tensors of 8 or 16 channels run the fused passes of include/vnet_hip_head.h (set_head_fusion(False): never); every
+    other case runs the two ops one after the other."""
+    a = ACT[act]
+    K = int(w.shape[-1])
+    C = int(w.shape[-2])
+    if _meta(x):
+        return torch.empty(x.shape[:-1] + (K,), device="meta")
+    fused = (_HEAD_FUSE["on"] and x.dtype == torch.float32 and not storage_is_bf16() and (residual is None or residual.dtype == torch.float32)
+             and int(x.shape[-1]) == C and (kind < 0 or residual is None) and _lib.lib().vnet_bn_head_ok(C, K))
+    if not fused:
+        if kind < 0:
+            y = bn_act(x, g1, b1, act, alpha, residual, False, moving[0], moving[1])
+        else:
+            y = bn_chain(x, kind, act, alpha, g1, b1, g2, b2, g3, b3, moving)
+        return head_conv(y, w, b)
+    _need_gpu(x, "bn_head")
+    if a == 2 and alpha is None:
+        raise VnetHipError("prelu needs alpha")
+    if kind == 0 and (g3 is None or b3 is None):
+        raise VnetHipError("bn_chain kind 0 needs three batch-norm layers")
+    stats = rows = None
+    if _HEAD_FUSE["stats"] and _SYNC_BN is None:
+        rows = _lib.lib().vnet_bn_head_stats_rows(x.numel() // C, C)
+        stats = torch.empty((rows, 2 * K), dtype=torch.float32, device=x.device)
+    logits = _BnHeadFn.apply(x, residual, int(kind), a, alpha if a == 2 else None, w, b, stats, tuple(moving), g1, b1, g2, b2, g3, b3)
+    if stats is not None:
+        logits._vnet_stats = _EpilogueStats(stats, rows, None)      # the batch-norm behind the head runs only its finalize
+    return logits
+
+
 def parse_loss(name):
     """Loss.Name -> kind bits (reference model.py:495-558)."""
     valid = ("xent", "weighted_xent", "sorensen", "weighted_sorensen", "jaccard", "weighted_jaccard",
