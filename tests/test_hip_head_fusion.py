@@ -252,11 +252,36 @@ def test_bn_head_op(dev, kind, C, K, act, res, shp):
     check_close(tag + " dw vs unfused", f["dw"], _f64(u["dw"]), 2e-6)
 
 
+def test_bn_head_leaves_its_ds_in_the_fork_slot(dev):
+    """bn_head over a forked residual (kind -1) leaves its ds in the residual's fork slot, fused or not, as bn_act does: the block
+    input's other consumer then accumulates its gradient into that tensor and no add kernel runs."""
+    from vnet_tensorflow_amd import ops
+    C, K, shp = 16, 2, (1, 4, 5, 6)
+    rng = np.random.default_rng(3)
+    for fused in (True, False):
+        x = g(rng.standard_normal(shp + (C,)), dev).requires_grad_(True)
+        _, r = ops.fork(g(rng.standard_normal(shp + (C,)), dev).requires_grad_(True))
+        slot, found = r._vnet_slot, []
+        r.register_hook(lambda gr: found.append(slot.first is not None and slot.first.data_ptr() == gr.data_ptr()))
+        par = [g(v, dev).requires_grad_(True) for v in (rng.standard_normal((1, 1, 1, C, K)), rng.standard_normal(K),
+                                                        rng.uniform(0.05, 0.3, C), rng.uniform(0.5, 1.5, C), rng.standard_normal(C))]
+        prev = ops.set_head_fusion(fused)
+        try:
+            lg = ops.bn_head(x, par[0], par[1], -1, "prelu", par[2], par[3], par[4], residual=r)
+            lg.backward(g(rng.standard_normal(shp + (K,)), dev))
+        finally:
+            ops.set_head_fusion(*prev)
+        assert found == [True], "fused %s: the residual's gradient is not in its fork slot" % fused
+        assert slot.first is None                        # (the fork node has run and dropped it)
+
+
 def test_network_takes_the_fused_head(dev):
     """networks.VNet with dropout 0 runs the fused passes and none of the head's own kernels; fuse_head = False or a dropout layer
     between the decoder and the head keeps the unfused ops.  With K = 2 the fused network computes the unfused network's bits:
-    logits and every parameter gradient."""
-    from vnet_tensorflow_amd import _lib, networks
+    logits and every parameter gradient -- with the decoder's chains in closed form and, fuse_bn_chains = False, with the head folded
+    into bn_act with the residual (kind -1).  No forked tensor's gradient needs an add kernel: its fork node finds the sum its second
+    consumer wrote, or a single gradient."""
+    from vnet_tensorflow_amd import _lib, networks, ops
     real_lib = _lib.lib
     real = real_lib()
     seen = []
@@ -266,31 +291,42 @@ def test_network_takes_the_fused_head(dev):
             seen.append(name)
             return getattr(real, name)
     rec = Rec()
+    fork_backward = ops._ForkFn.backward
+    forks = []
+
+    def watched(ctx, ga, gb):
+        forks.append(ctx.slot.total is not None or ga is None or gb is None)
+        return fork_backward(ctx, ga, gb)
     fused_names = {"vnet_bn_act_head_fwd", "vnet_bn_act_bwd_reduce_head", "vnet_bn_act_bwd_apply_head"}
     images, _ = O.synthetic_batch(1, 16, 1, 2, seed=7)
     out = {}
-    for fuse, rate in ((True, 0.0), (False, 0.0), (True, 0.25)):
+    for fuse, rate, chains in ((True, 0.0, True), (False, 0.0, True), (True, 0.25, True), (True, 0.0, False), (False, 0.0, False)):
         for nconv in ((1, 2), (2, 2)):                       # the level-1 decoder block ends in chain kind 0 / kind 1
             np.random.seed(5)                                # (the initialisers draw from NumPy's global generator)
             net = networks.VNet(2, rate, 8, 2, nconv, 2, True, "prelu", device=dev)
-            net.fuse_head = fuse
+            net.fuse_head, net.fuse_bn_chains = fuse, chains
             net.build((1, 16, 16, 16, 1))
-            del seen[:]
+            del seen[:], forks[:]
             _lib.lib = lambda: rec
+            ops._ForkFn.backward = staticmethod(watched)
             try:
                 logits = net.GetNetwork(torch.from_numpy(images).to(dev))
                 logits.square().sum().backward()
             finally:
                 _lib.lib = real_lib
+                ops._ForkFn.backward = staticmethod(fork_backward)
             names = set(seen)
             if fuse and rate == 0.0:
                 assert fused_names <= names and not {"vnet_head_fwd", "vnet_head_bwd"} & names, sorted(names)
             else:
                 assert {"vnet_head_fwd", "vnet_head_bwd"} <= names and not fused_names & names, sorted(names)
+            assert ("vnet_bn_chain_coef_fwd" in names) == chains
+            assert forks and all(forks), forks
             assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in net.parameters())
-            out[(fuse, rate, nconv)] = (logits.detach().clone(), [(n, p.grad.clone()) for n, p in net.named_parameters()])
-    for nconv in ((1, 2), (2, 2)):
-        (lf, gf), (lu, gu) = out[(True, 0.0, nconv)], out[(False, 0.0, nconv)]
-        assert torch.equal(lf, lu), "logits of the fused network differ from the unfused one's"
-        for (n, a1), (_, a0) in zip(gf, gu):
-            assert torch.equal(a1, a0), "gradient of %s differs between the fused and the unfused network" % n
+            out[(fuse, rate, chains, nconv)] = (logits.detach().clone(), [(n, p.grad.clone()) for n, p in net.named_parameters()])
+    for chains in (True, False):
+        for nconv in ((1, 2), (2, 2)):
+            (lf, gf), (lu, gu) = out[(True, 0.0, chains, nconv)], out[(False, 0.0, chains, nconv)]
+            assert torch.equal(lf, lu), "logits of the fused network differ from the unfused one's"
+            for (n, a1), (_, a0) in zip(gf, gu):
+                assert torch.equal(a1, a0), "gradient of %s differs between the fused and the unfused network" % n

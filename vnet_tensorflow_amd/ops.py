@@ -1282,14 +1282,53 @@ def _bn_stats(rt, x, r, bcast, M, C, mm, mv, pre=None):
     return mean, invstd, float(M) * world
 
 
-def _bn_backward(rt, dy, x, r, bcast, M, C, mean, invstd, scale, shift, act, alpha, dscale, dshift, dalpha, ds, m_total,
-                 all_reduce=None, coef=None, head=None):
-    """Backward of y = act(scale * xhat + shift), xhat the normalised s = x (+ r): the sums sum_dz_xhat -> dscale, sum_dz -> dshift
-    (and dalpha), all-reduced when rt says so, then ds (None: no data gradient) from them.  coef(sum_dz_xhat) runs between the two
-    and returns the apply's xhat coefficient (the chain's vnet_bn_chain_coef_bwd).
-    head = (w, dw, db): y feeds the 1x1x1 head y W + b and `dy` is the gradient of its LOGITS -- both passes form dy = dlogits W^T
-    per voxel and the first one also sums the head's dw / db (include/vnet_hip_head.h; float32, rt.stats not "small")."""
+def _bn_forward(op, x, r, bcast, C, pre, scale, shift, act, alpha, mm, mv, coef=None, head=None):
+    """Forward of y = act(scale * xhat + shift), xhat the normalised s = x (+ r) (both contiguous; pre: _epilogue_of the caller's x):
+    the route, the statistics and ONE normalise launch -- every batch-norm's forward goes through here.  coef(mean, invstd) runs between
+    the two and returns the (scale, shift) to use (the chain's coefficients, _BnFn).  head = (w, b, stats): the launch is the fused
+    head's -- it returns the logits y W + b in place of y, which it does not store, and writes the logits' partial sums into stats
+    (None: not) (include/vnet_hip_head.h; float32 only).
+    Returns the plan _bn_backward takes -- (route, bcast, M, C, act, rows the statistics cover, the backward's all-reduce or None) --
+    and y, mean, invstd, scale, shift."""
     L = _lib.lib()
+    M = x.numel() if bcast else x.numel() // C
+    rt = bn_route(op, M, C, bcast, _is16(x), None if r is None else _is16(r), pre is not None)
+    if rt.apply16 and r is not None and not _is16(r):
+        raise VnetHipError("bn_act: bf16 and float32 tensors mixed")
+    dev = x.device
+    if rt.stats == "small":
+        mean = torch.empty(C, dtype=torch.float32, device=dev)
+        invstd = torch.empty(C, dtype=torch.float32, device=dev)
+        y = torch.empty(x.shape, dtype=torch.bfloat16, device=dev)
+        check(L.vnet_bn_small_fwd_b16(_ptr(x), _ptr(r), M, C, BN_EPS, BN_MOMENTUM, _ptr(scale), _ptr(shift), act, _ptr(alpha),
+                                      _ptr(mean), _ptr(invstd), _ptr(mm), _ptr(mv), _ptr(y), _stream()), "vnet_bn_small_fwd_b16")
+        m_total = float(M)
+    else:
+        mean, invstd, m_total = _bn_stats(rt, x, r, bcast, M, C, mm, mv, pre)
+        if coef is not None:
+            scale, shift = coef(mean, invstd)
+        bn = (M, C, _ptr(mean), _ptr(invstd), _ptr(scale), _ptr(shift), act, _ptr(alpha))
+        if head is not None:
+            w, b, stats = head
+            K = int(w.shape[-1])
+            y = torch.empty(x.shape[:-1] + (K,), dtype=torch.float32, device=dev)
+            check(L.vnet_bn_act_head_fwd(_ptr(x), _ptr(r), *bn, _ptr(w), _ptr(b), K, None, _ptr(y), _ptr(stats), _stream()),
+                  "vnet_bn_act_head_fwd")
+        else:
+            y = torch.empty(x.shape[:-1] + (C,), dtype=torch.bfloat16 if rt.apply16 else torch.float32, device=dev)
+            name = "vnet_bn_act_fwd" + ("_b16" if rt.apply16 else "")
+            check(getattr(L, name)(_ptr(x), _ptr(r), int(bcast), *bn, _ptr(y), _stream()), name)
+    return (rt, bcast, M, C, act, m_total, _SYNC_BN[0] if rt.allreduce else None), y, mean, invstd, scale, shift
+
+
+def _bn_backward(plan, dy, x, r, mean, invstd, scale, shift, alpha, dscale, dshift, dalpha, ds, coef=None, head=None):
+    """Backward of _bn_forward's y (plan: what it returned): the sums sum_dz_xhat -> dscale, sum_dz -> dshift (and dalpha), all-reduced
+    when the route says so, then ds (None: no data gradient) from them.  coef(sum_dz_xhat) runs between the two and returns the apply's
+    xhat coefficient (the chain's, _BnFn).
+    head = (w, dw, db): y fed the 1x1x1 head y W + b and `dy` is the gradient of its LOGITS -- both passes form dy = dlogits W^T
+    per voxel and the first one also sums the head's dw / db (include/vnet_hip_head.h; float32, the route not "small")."""
+    L = _lib.lib()
+    rt, bcast, M, C, act, m_total, all_reduce = plan
     if head is not None:
         w, dw, db = head
         K = int(w.shape[-1])
@@ -1323,124 +1362,92 @@ def _bn_backward(rt, dy, x, r, bcast, M, C, mean, invstd, scale, shift, act, alp
         check(getattr(L, name)(*args, _ptr(sdz), _ptr(sdzx), m_total, _ptr(extra), _ptr(ds), _stream()), name)
 
 
-class _BnActFn(torch.autograd.Function):
+class _BnFn(torch.autograd.Function):
+    """The batch-norm behind bn_act, bn_chain and bn_head: one statistics pass + one normalise pass forward, one reduce + one apply pass
+    backward.  kind -1: y = act(BN(x (+ r))) with (g1, b1), x tiled from one channel when bcast.  The decoder's chains in closed form
+    (include/vnet_hip.h, vnet_bn_chain_*) -- kind 0: act(BN3(BN1(x) + BN2(BN1(x)))) (networks.py:333-337), kind 1: act(BNb(x + BNa(x)))
+    with (g1, b1) = a, (g2, b2) = b (networks.py:358-361).  bufs: the moving averages (mm1, mv1, ... mv3).
+    With w (float32 only) the result is logits = head_conv(y, w, b) from the same normalise pass, which also writes the partial sums of
+    the logits into `stats` (None: not) for the batch-norm behind the head.  y is then not stored: nothing but the head reads it, and
+    the backward rebuilds it from x; its two passes read dlogits (K floats per voxel) in place of a [M][C] gradient of y, and the reduce
+    also sums the head's dw / db.  Returns (y or logits, mean, invstd)."""
+
     @staticmethod
-    def forward(ctx, x, r, gamma, beta, alpha, act, bcast, mm, mv):
+    def forward(ctx, x, r, kind, act, bcast, stats, bufs, alpha, w, b, g1, b1, g2, b2, g3, b3):
         L = _lib.lib()
         ctx.slot_r = getattr(r, "_vnet_slot", None)
-        C = gamma.numel()
+        C = g1.numel()
         pre = _epilogue_of(x, r, C)
         x = x.contiguous()
         r = r.contiguous() if r is not None else None
-        M = x.numel() if bcast else x.numel() // C
-        ctx.rt = rt = bn_route("act", M, C, bcast, _is16(x), None if r is None else _is16(r), pre is not None)
-        if rt.apply16 and r is not None and not _is16(r):
-            raise VnetHipError("bn_act: bf16 and float32 tensors mixed")
-        y = torch.empty(x.shape[:-1] + (C,), dtype=torch.bfloat16 if rt.apply16 else torch.float32, device=x.device)
-        if rt.stats == "small":
-            mean = torch.empty(C, dtype=torch.float32, device=x.device)
-            invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-            check(L.vnet_bn_small_fwd_b16(_ptr(x), _ptr(r), M, C, BN_EPS, BN_MOMENTUM, _ptr(gamma), _ptr(beta), act, _ptr(alpha),
-                                          _ptr(mean), _ptr(invstd), _ptr(mm), _ptr(mv), _ptr(y), _stream()), "vnet_bn_small_fwd_b16")
-            ctx.m_total = float(M)
-        else:
-            mean, invstd, ctx.m_total = _bn_stats(rt, x, r, bcast, M, C, mm, mv, pre)
-            name = "vnet_bn_act_fwd" + ("_b16" if rt.apply16 else "")
-            check(getattr(L, name)(_ptr(x), _ptr(r), int(bcast), M, C, _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta),
-                                   act, _ptr(alpha), _ptr(y), _stream()), name)
-        ctx.all_reduce = _SYNC_BN[0] if rt.allreduce else None
-        ctx.save_for_backward(x, r, gamma, beta, alpha, mean, invstd)
-        ctx.params = (gamma, beta, alpha)
-        ctx.cfg = (act, bcast, M, C)
+        mm1, mv1, mm2, mv2, mm3, mv3 = bufs
+
+        def coef(mean, invstd):     # the chain as ONE scale / shift per channel, and the moving averages of its derived layers
+            ceff = torch.empty(C, dtype=torch.float32, device=x.device)
+            deff = torch.empty(C, dtype=torch.float32, device=x.device)
+            name = "vnet_bn_chain_coef_fwd"
+            check(getattr(L, name)(kind, C, BN_EPS, BN_MOMENTUM, _ptr(mean), _ptr(invstd), _ptr(g1), _ptr(b1), _ptr(g2), _ptr(b2), _ptr(g3),
+                                   _ptr(b3), _ptr(ceff), _ptr(deff), _ptr(mm2), _ptr(mv2), _ptr(mm3), _ptr(mv3), _stream()), name)
+            return ceff, deff
+        ctx.plan, y, mean, invstd, scale, shift = _bn_forward("act" if kind < 0 else "chain", x, r, bcast, C, pre, g1, b1, act, alpha,
+                                                              mm1, mv1, coef if kind >= 0 else None, (w, b, stats) if w is not None else None)
+        ctx.save_for_backward(x, r, alpha, w, g1, g2, g3, mean, invstd, scale, shift)
+        ctx.params = (g1, b1, g2, b2, g3, b3, alpha, w, b)
+        ctx.kind = kind
         ctx.mark_non_differentiable(mean, invstd)
         ctx.set_materialize_grads(False)      # no zero-filled gradients for the (non-differentiable) statistics outputs
         return y, mean, invstd
 
     @staticmethod
     def backward(ctx, dy, _gmean, _ginvstd):
-        x, r, gamma, beta, alpha, mean, invstd = ctx.saved_tensors
-        act, bcast, M, C = ctx.cfg
+        L = _lib.lib()
+        x, r, alpha, w, g1, g2, g3, mean, invstd, scale, shift = ctx.saved_tensors
+        rt, bcast, _, C, _, m_total, _ = ctx.plan
+        kind = ctx.kind
         dy = dy.contiguous()
-        if ctx.rt.apply16 and not _is16(dy):
+        if rt.apply16 and not _is16(dy):
             raise VnetHipError("bn_act backward: expected a bfloat16 gradient")
-        gref, bref, aref = ctx.params
-        dgamma, sg = _grad_out(gref)
-        dbeta, sbt = _grad_out(bref)
-        dalpha, sa = _grad_out(aref) if alpha is not None else (None, None)
+        dev = dy.device
+        # every parameter's gradient goes straight into its sink where there is one (_grad_out here, _grad_ret below)
+        outs = [_grad_out(p) if p is not None else (None, None) for p in ctx.params]
+        dg1, db1, dg2, db2, dg3, db3, dalpha, dw, db = (o[0] for o in outs)
+        dscale, dshift, coef = dg1, db1, None
+        if kind >= 0:
+            dscale = torch.empty(C, dtype=torch.float32, device=dev)
+            dshift = torch.empty(C, dtype=torch.float32, device=dev)
+            extra = torch.empty(C, dtype=torch.float32, device=dev)
+
+            def coef(dCg):        # every gamma / beta gradient of the chain, and the xhat coefficient of the apply
+                name = "vnet_bn_chain_coef_bwd"
+                check(getattr(L, name)(kind, C, BN_EPS, m_total, _ptr(mean), _ptr(invstd), _ptr(g1), _ptr(g2), _ptr(g3), _ptr(dscale),
+                                       _ptr(dshift), _ptr(dCg), _ptr(dg1), _ptr(db1), _ptr(dg2), _ptr(db2), _ptr(dg3), _ptr(db3), _ptr(extra),
+                                       _stream()), name)
+                return extra
         need_ds = ctx.needs_input_grad[0] or (r is not None and ctx.needs_input_grad[1])
-        ds = torch.empty(dy.shape, dtype=torch.bfloat16 if ctx.rt.apply16 else torch.float32, device=dy.device) if need_ds else None
-        _bn_backward(ctx.rt, dy, x, r, bcast, M, C, mean, invstd, gamma, beta, act, alpha, dgamma, dbeta, dalpha, ds, ctx.m_total,
-                     ctx.all_reduce)
-        th = getattr(gref, "_vnet_deferred", None)
-        if th is not None and sg is not None and sbt is not None:
-            del gref._vnet_deferred
+        ds = torch.empty(x.shape[:-1] + (C,), dtype=torch.bfloat16 if rt.apply16 else torch.float32, device=dev) if need_ds else None
+        _bn_backward(ctx.plan, dy, x, r, mean, invstd, scale, shift, alpha, dscale, dshift, dalpha, ds, coef,
+                     (w, dw, db) if w is not None else None)
+        th = getattr(ctx.params[0], "_vnet_deferred", None)
+        if th is not None and outs[0][1] is not None and outs[1][1] is not None:
+            del ctx.params[0]._vnet_deferred
             th(1)                                          # the fused input conv adds its share of dgamma / dbeta (see _InputConvFn)
         dx = ds
         if bcast and ds is not None:
             dx = colsum_rows(ds)
         if r is not None and ds is not None and ctx.slot_r is not None and ctx.slot_r.first is None:
             ctx.slot_r.first = ds                      # the block input's other consumer (conv_1) adds its gradient into this
-        return dx, (ds if r is not None else None), _grad_ret(dgamma, sg), _grad_ret(dbeta, sbt), _grad_ret(dalpha, sa), None, None, None, None
+        rets = [_grad_ret(t, s) if p is not None else None for (t, s), p in zip(outs, ctx.params)]
+        return (dx, (ds if r is not None else None), None, None, None, None, None, rets[6], rets[7], rets[8]) + tuple(rets[:6])
 
 
-class _BnChainFn(torch.autograd.Function):
-    """Decoder batch-norm chains in closed form (include/vnet_hip.h, vnet_bn_chain_*):
-    kind 0: act(BN3(BN1(x) + BN2(BN1(x))))   (networks.py:333-337)      kind 1: act(BNb(x + BNa(x)))   (networks.py:358-361)
-    One statistics pass + one normalise pass forward, one reduce + one apply pass backward."""
-
-    @staticmethod
-    def forward(ctx, x, kind, act, alpha, g1, b1, g2, b2, g3, b3, bufs):
-        L = _lib.lib()
-        C = g1.numel()
-        pre = _epilogue_of(x, None, C)
-        x = x.contiguous()
-        M = x.numel() // C
-        dev = x.device
-        mm1, mv1, mm2, mv2, mm3, mv3 = bufs
-        ctx.rt = rt = bn_route("chain", M, C, x16=_is16(x), epilogue=pre is not None)
-        mean, invstd, ctx.m_total = _bn_stats(rt, x, None, False, M, C, mm1, mv1, pre)
-        ctx.all_reduce = _SYNC_BN[0] if rt.allreduce else None
-        ceff = torch.empty(C, dtype=torch.float32, device=dev)
-        deff = torch.empty(C, dtype=torch.float32, device=dev)
-        check(L.vnet_bn_chain_coef_fwd(kind, C, BN_EPS, BN_MOMENTUM, _ptr(mean), _ptr(invstd), _ptr(g1), _ptr(b1), _ptr(g2), _ptr(b2),
-                                       _ptr(g3), _ptr(b3), _ptr(ceff), _ptr(deff), _ptr(mm2), _ptr(mv2), _ptr(mm3), _ptr(mv3),
-                                       _stream()), "vnet_bn_chain_coef_fwd")
-        y = torch.empty(x.shape, dtype=torch.bfloat16 if rt.apply16 else torch.float32, device=dev)
-        name = "vnet_bn_act_fwd" + ("_b16" if rt.apply16 else "")
-        check(getattr(L, name)(_ptr(x), None, 0, M, C, _ptr(mean), _ptr(invstd), _ptr(ceff), _ptr(deff), act, _ptr(alpha), _ptr(y),
-                               _stream()), name)
-        ctx.save_for_backward(x, alpha, g1, g2, g3, mean, invstd, ceff, deff)
-        ctx.params = (alpha, g1, b1, g2, b2, g3, b3)
-        ctx.cfg = (kind, act, M, C)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        L = _lib.lib()
-        x, alpha, g1, g2, g3, mean, invstd, ceff, deff = ctx.saved_tensors
-        kind, act, M, C = ctx.cfg
-        aref, g1r, b1r, g2r, b2r, g3r, b3r = ctx.params
-        dy = dy.contiguous()
-        dev = dy.device
-        dC = torch.empty(C, dtype=torch.float32, device=dev)
-        dD = torch.empty(C, dtype=torch.float32, device=dev)
-        dalpha, sa = _grad_out(aref) if alpha is not None else (None, None)
-        outs = [_grad_out(r) if r is not None else (None, None) for r in (g1r, b1r, g2r, b2r, g3r, b3r)]
-        (dg1, s1), (db1, t1), (dg2, s2), (db2, t2), (dg3, s3), (db3, t3) = outs
-        extra = torch.empty(C, dtype=torch.float32, device=dev)
-        dx = torch.empty(dy.shape, dtype=torch.bfloat16 if ctx.rt.apply16 else torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-
-        def coef(dCg):        # every gamma / beta gradient of the chain, and the xhat coefficient of the apply
-            check(L.vnet_bn_chain_coef_bwd(kind, C, BN_EPS, ctx.m_total, _ptr(mean), _ptr(invstd), _ptr(g1), _ptr(g2), _ptr(g3),
-                                           _ptr(dC), _ptr(dD), _ptr(dCg), _ptr(dg1), _ptr(db1), _ptr(dg2), _ptr(db2), _ptr(dg3),
-                                           _ptr(db3), _ptr(extra), _stream()), "vnet_bn_chain_coef_bwd")
-            return extra
-        _bn_backward(ctx.rt, dy, x, None, False, M, C, mean, invstd, ceff, deff, act, alpha, dC, dD, dalpha, dx, ctx.m_total,
-                     ctx.all_reduce, coef)
-        g3ret = _grad_ret(dg3, s3) if g3r is not None else None
-        b3ret = _grad_ret(db3, t3) if b3r is not None else None
-        return (dx, None, None, _grad_ret(dalpha, sa) if alpha is not None else None, _grad_ret(dg1, s1), _grad_ret(db1, t1),
-                _grad_ret(dg2, s2), _grad_ret(db2, t2), g3ret, b3ret, None)
+def _bn_apply(what, x, r, kind, a, alpha, bcast, g, moving, w=None, b=None, stats=None):
+    """The argument checks bn_act, bn_chain and bn_head (`what`) share, then _BnFn; g = (g1, b1, g2, b2, g3, b3)."""
+    _need_gpu(x, what, allow16=w is None)
+    if a == 2 and alpha is None:
+        raise VnetHipError("prelu needs alpha")
+    if kind == 0 and (g[4] is None or g[5] is None):
+        raise VnetHipError("bn_chain kind 0 needs three batch-norm layers")
+    return _BnFn.apply(x, r, int(kind), a, bool(bcast), stats, tuple(moving), alpha if a == 2 else None, w, b, *g)
 
 
 def bn_chain(x, kind, act, alpha, g1, b1, g2, b2, g3=None, b3=None, moving=(None,) * 6):
@@ -1449,12 +1456,7 @@ def bn_chain(x, kind, act, alpha, g1, b1, g2, b2, g3=None, b3=None, moving=(None
     a = ACT[act]
     if _meta(x):
         return torch.empty(x.shape, device="meta")
-    _need_gpu(x, "bn_chain", allow16=True)
-    if a == 2 and alpha is None:
-        raise VnetHipError("prelu needs alpha")
-    if kind == 0 and (g3 is None or b3 is None):
-        raise VnetHipError("bn_chain kind 0 needs three batch-norm layers")
-    return _BnChainFn.apply(x, int(kind), a, alpha if a == 2 else None, g1, b1, g2, b2, g3, b3, tuple(moving))
+    return _bn_apply("bn_chain", x, None, kind, a, alpha, False, (g1, b1, g2, b2, g3, b3), moving)[0]
 
 
 def colsum_rows(ds):
@@ -1471,10 +1473,8 @@ def bn_act(x, gamma, beta, act=None, alpha=None, residual=None, tile=False, movi
     if _meta(x):
         y = torch.empty(x.shape[:-1] + (gamma.numel(),), device="meta")
         return (y, None, None) if want_stats else y
-    _need_gpu(x, "bn_act", allow16=True)
-    if a == 2 and alpha is None:
-        raise VnetHipError("prelu needs alpha")
-    y, mean, invstd = _BnActFn.apply(x, residual, gamma, beta, alpha if a == 2 else None, a, bool(tile), moving_mean, moving_var)
+    y, mean, invstd = _bn_apply("bn_act", x, residual, -1, a, alpha, tile, (gamma, beta) + (None,) * 4,
+                                (moving_mean, moving_var) + (None,) * 4)
     return (y, mean, invstd) if want_stats else y
 
 
@@ -1496,24 +1496,16 @@ def bn_update_only(x, C, moving_mean, moving_var):
 class _BnConcatFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, x1, gamma, beta, mm, mv):
-        L = _lib.lib()
         ctx.slot1 = getattr(x1, "_vnet_slot", None)
-        x0, x1 = x0.contiguous(), x1.contiguous()
-        M = x0.numel() // x0.shape[-1]
         ys, saved, ctx.halves, off = [], [], [], 0
-        for x in (x0, x1):
+        for x in (x0.contiguous(), x1.contiguous()):
             C = x.shape[-1]
-            rt = bn_route("act", M, C, x16=_is16(x))
             sl = slice(off, off + C)
-            mean, invstd, m_total = _bn_stats(rt, x, None, False, M, C, mm[sl] if mm is not None else None,
-                                              mv[sl] if mv is not None else None)
-            y = torch.empty_like(x)
-            name = "vnet_bn_act_fwd" + ("_b16" if rt.apply16 else "")
-            check(getattr(L, name)(_ptr(x), None, 0, M, C, _ptr(mean), _ptr(invstd), _ptr(gamma[sl]), _ptr(beta[sl]), 0, None, _ptr(y),
-                                   _stream()), name)
+            plan, y, mean, invstd, _, _ = _bn_forward("act", x, None, False, C, None, gamma[sl], beta[sl], 0, None,
+                                                      mm[sl] if mm is not None else None, mv[sl] if mv is not None else None)
             ys.append(y)
             saved += [x, mean, invstd]
-            ctx.halves.append((rt, sl, M, C, m_total, _SYNC_BN[0] if rt.allreduce else None))
+            ctx.halves.append((plan, sl))
             off += C
         ctx.save_for_backward(gamma, beta, *saved)
         ctx.params = (gamma, beta)
@@ -1526,12 +1518,11 @@ class _BnConcatFn(torch.autograd.Function):
         dgamma, sg = _grad_out(gref)
         dbeta, sbt = _grad_out(bref)
         out = []
-        for k, (dy, (rt, sl, M, C, m_total, all_reduce)) in enumerate(zip((dy0, dy1), ctx.halves)):
+        for k, (dy, (plan, sl)) in enumerate(zip((dy0, dy1), ctx.halves)):
             x, mean, invstd = ctx.saved_tensors[2 + 3 * k:5 + 3 * k]
             dy = dy.contiguous()
             ds = torch.empty_like(dy) if ctx.needs_input_grad[k] else None
-            _bn_backward(rt, dy, x, None, False, M, C, mean, invstd, gamma[sl], beta[sl], 0, None, dgamma[sl], dbeta[sl], None, ds,
-                         m_total, all_reduce)
+            _bn_backward(plan, dy, x, None, mean, invstd, gamma[sl], beta[sl], None, dgamma[sl], dbeta[sl], None, ds)
             out.append(ds)
         if out[1] is not None and ctx.slot1 is not None and ctx.slot1.first is None:
             ctx.slot1.first = out[1]                     # the skip feature's other consumer (the max-pooling) adds its gradient into this
@@ -1678,7 +1669,6 @@ def head_conv(x, w, b):
     return _HeadFn.apply(x, w, b)
 
 
-# ---- fused softmax + Dice / cross-entropy loss ---------------------------------------------------------------
 # ---- the decoder's last batch-norm with the head folded in (include/vnet_hip_head.h) ---------------------------------------------
 # "stats": the normalise pass also writes the statistics rows of the logits, so the batch-norm behind the head runs only its finalize
 # (12 us and a launch at 128^3).  Off: those rows group the voxels differently from vnet_bn_stats, mean / invstd move in the last
@@ -1695,79 +1685,6 @@ def set_head_fusion(on, stats=None):
     if stats is not None:
         _HEAD_FUSE["stats"] = bool(stats)
     return prev
-
-
-class _BnHeadFn(torch.autograd.Function):
-    """logits = head_conv(y), y the output of bn_chain(x, kind, ...) (kind 0 / 1) or of bn_act(x, g1, b1, act, alpha, residual=r)
-    (kind -1), in one normalise pass that also writes the partial sums of the logits into `stats` (None: not) for the batch-norm
-    behind the head.  y is not stored: nothing but the head reads it, and the backward rebuilds it from x.  Backward: one reduce and one apply
-    pass read dlogits (K floats per voxel) in place of a [M][C] gradient of y; the reduce also sums the head's dw / db."""
-
-    @staticmethod
-    def forward(ctx, x, r, kind, act, alpha, w, b, stats, bufs, g1, b1, g2, b2, g3, b3):
-        L = _lib.lib()
-        C, K = int(w.shape[-2]), int(w.shape[-1])
-        pre = _epilogue_of(x, r, C)
-        x = x.contiguous()
-        r = r.contiguous() if r is not None else None
-        M = x.numel() // C
-        dev = x.device
-        mm1, mv1, mm2, mv2, mm3, mv3 = bufs
-        if kind < 0:
-            ctx.rt = rt = bn_route("act", M, C, False, False, None if r is None else False, pre is not None)
-        else:
-            ctx.rt = rt = bn_route("chain", M, C, x16=False, epilogue=pre is not None)
-        mean, invstd, ctx.m_total = _bn_stats(rt, x, r, False, M, C, mm1, mv1, pre)
-        ctx.all_reduce = _SYNC_BN[0] if rt.allreduce else None
-        scale, shift = g1, b1
-        if kind >= 0:
-            scale = torch.empty(C, dtype=torch.float32, device=dev)
-            shift = torch.empty(C, dtype=torch.float32, device=dev)
-            check(L.vnet_bn_chain_coef_fwd(kind, C, BN_EPS, BN_MOMENTUM, _ptr(mean), _ptr(invstd), _ptr(g1), _ptr(b1), _ptr(g2), _ptr(b2),
-                                           _ptr(g3), _ptr(b3), _ptr(scale), _ptr(shift), _ptr(mm2), _ptr(mv2), _ptr(mm3), _ptr(mv3),
-                                           _stream()), "vnet_bn_chain_coef_fwd")
-        logits = torch.empty(x.shape[:-1] + (K,), dtype=torch.float32, device=dev)
-        check(L.vnet_bn_act_head_fwd(_ptr(x), _ptr(r), M, C, _ptr(mean), _ptr(invstd), _ptr(scale), _ptr(shift), act, _ptr(alpha),
-                                     _ptr(w), _ptr(b), K, None, _ptr(logits), _ptr(stats), _stream()), "vnet_bn_act_head_fwd")
-        ctx.save_for_backward(x, r, alpha, w, g1, g2, g3, mean, invstd, scale, shift)
-        ctx.params = (alpha, w, b, g1, b1, g2, b2, g3, b3)
-        ctx.cfg = (kind, act, M, C)
-        return logits
-
-    @staticmethod
-    def backward(ctx, dl):
-        L = _lib.lib()
-        x, r, alpha, w, g1, g2, g3, mean, invstd, scale, shift = ctx.saved_tensors
-        kind, act, M, C = ctx.cfg
-        aref, wref, bref, g1r, b1r, g2r, b2r, g3r, b3r = ctx.params
-        dl = dl.contiguous()
-        dev = dl.device
-        dw, sw = _grad_out(wref)
-        db, sb = _grad_out(bref)
-        dalpha, sa = _grad_out(aref) if alpha is not None else (None, None)
-        need_ds = ctx.needs_input_grad[0] or (r is not None and ctx.needs_input_grad[1])
-        ds = torch.empty(x.shape, dtype=torch.float32, device=dev) if need_ds else None
-        outs = [_grad_out(p) if p is not None else (None, None) for p in (g1r, b1r, g2r, b2r, g3r, b3r)]
-        (dg1, s1), (db1, t1), (dg2, s2), (db2, t2), (dg3, s3), (db3, t3) = outs
-        if kind < 0:
-            _bn_backward(ctx.rt, dl, x, r, False, M, C, mean, invstd, scale, shift, act, alpha, dg1, db1, dalpha, ds, ctx.m_total,
-                         ctx.all_reduce, head=(w, dw, db))
-        else:
-            dC = torch.empty(C, dtype=torch.float32, device=dev)
-            dD = torch.empty(C, dtype=torch.float32, device=dev)
-            extra = torch.empty(C, dtype=torch.float32, device=dev)
-
-            def coef(dCg):        # every gamma / beta gradient of the chain, and the xhat coefficient of the apply
-                check(L.vnet_bn_chain_coef_bwd(kind, C, BN_EPS, ctx.m_total, _ptr(mean), _ptr(invstd), _ptr(g1), _ptr(g2), _ptr(g3),
-                                               _ptr(dC), _ptr(dD), _ptr(dCg), _ptr(dg1), _ptr(db1), _ptr(dg2), _ptr(db2), _ptr(dg3),
-                                               _ptr(db3), _ptr(extra), _stream()), "vnet_bn_chain_coef_bwd")
-                return extra
-            _bn_backward(ctx.rt, dl, x, None, False, M, C, mean, invstd, scale, shift, act, alpha, dC, dD, dalpha, ds, ctx.m_total,
-                         ctx.all_reduce, coef, head=(w, dw, db))
-        ret = [_grad_ret(g, s_) if p is not None else None
-               for g, s_, p in ((dg1, s1, g1r), (db1, t1, b1r), (dg2, s2, g2r), (db2, t2, b2r), (dg3, s3, g3r), (db3, t3, b3r))]
-        return (ds, (ds if r is not None else None), None, None, _grad_ret(dalpha, sa) if alpha is not None else None,
-                _grad_ret(dw, sw), _grad_ret(db, sb), None, None) + tuple(ret)
 
 
 def bn_head(x, w, b, kind, act, alpha, g1, b1, g2=None, b2=None, g3=None, b3=None, residual=None, moving=(None,) * 6):
@@ -1788,21 +1705,17 @@ def bn_head(x, w, b, kind, act, alpha, g1, b1, g2=None, b2=None, g3=None, b3=Non
         else:
             y = bn_chain(x, kind, act, alpha, g1, b1, g2, b2, g3, b3, moving)
         return head_conv(y, w, b)
-    _need_gpu(x, "bn_head")
-    if a == 2 and alpha is None:
-        raise VnetHipError("prelu needs alpha")
-    if kind == 0 and (g3 is None or b3 is None):
-        raise VnetHipError("bn_chain kind 0 needs three batch-norm layers")
     stats = rows = None
     if _HEAD_FUSE["stats"] and _SYNC_BN is None:
         rows = _lib.lib().vnet_bn_head_stats_rows(x.numel() // C, C)
         stats = torch.empty((rows, 2 * K), dtype=torch.float32, device=x.device)
-    logits = _BnHeadFn.apply(x, residual, int(kind), a, alpha if a == 2 else None, w, b, stats, tuple(moving), g1, b1, g2, b2, g3, b3)
+    logits = _bn_apply("bn_head", x, residual, kind, a, alpha, False, (g1, b1, g2, b2, g3, b3), moving, w, b, stats)[0]
     if stats is not None:
         logits._vnet_stats = _EpilogueStats(stats, rows, None)      # the batch-norm behind the head runs only its finalize
     return logits
 
 
+# ---- fused softmax + Dice / cross-entropy loss ---------------------------------------------------------------
 def parse_loss(name):
     """Loss.Name -> kind bits (reference model.py:495-558)."""
     valid = ("xent", "weighted_xent", "sorensen", "weighted_sorensen", "jaccard", "weighted_jaccard",
