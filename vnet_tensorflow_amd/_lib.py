@@ -1,4 +1,5 @@
-"""ctypes binding of libvnet_hip.so (include/vnet_hip.h, include/vnet_hip_unet.h, include/vnet_hip_head.h).
+"""ctypes binding of libvnet_hip.so (include/vnet_hip.h, include/vnet_hip_unet.h, include/vnet_hip_head.h,
+include/vnet_hip_resample.h).
 
 The library is the product: there is NO fallback.  If the shared object is missing, or a
 kernel reports an error, this module raises -- nothing silently routes to PyTorch or the CPU.
@@ -142,6 +143,12 @@ SIGNATURES_HEAD = {
     "vnet_bn_act_bwd_apply_head": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
 }
 
+# fourth public header, include/vnet_hip_resample.h (the Resample transform and the way back of evaluate), same library
+SIGNATURES_RESAMPLE = {
+    "vnet_resample_linear": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _vp]),
+    "vnet_resample_nearest_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, _d, _vp]),
+}
+
 
 class WgradJob(ctypes.Structure):
     """include/vnet_hip.h: vnet_wgrad_job (one layer of vnet_conv_wgrad_b16_group)."""
@@ -199,7 +206,7 @@ def lib():
                 setattr(L, name, _memo(fn, (b"BF16_DEEP", b"BF16_DEEP_TARGET"), L))     # (the kernel choice follows these options)
             elif name.endswith("_ws_bytes") or name.endswith("_stats_rows") or name == "vnet_conv_stats_from_reduce" or name == "vnet_packed_weight_floats":
                 setattr(L, name, _memo(fn))    # pure size queries, asked before every launch: answer repeats from a dict
-        for name, (res, args) in list(SIGNATURES_UNET.items()) + list(SIGNATURES_HEAD.items()):
+        for name, (res, args) in list(SIGNATURES_UNET.items()) + list(SIGNATURES_HEAD.items()) + list(SIGNATURES_RESAMPLE.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
             if name in ("vnet_bn_head_ok", "vnet_bn_head_stats_rows", "vnet_bn_head_ws_bytes"):

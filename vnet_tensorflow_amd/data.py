@@ -4,9 +4,9 @@
 [X,Y,Z] remapped to class *indices* of SegmentationClasses (NiftiDataset3D.py:125-137).
 
 Sources: a case directory tree holding `.npy` or uncompressed NIfTI-1 `.nii` files, or the
-synthetic generator of SURVEY.md 8(d) (the shipped sample volumes are Git-LFS stubs).  The
-SimpleITK resampling transforms of the YAML pipeline are out of scope (SURVEY section 2 rows 10-12);
-only the pure index-math RandomCrop to PatchShape is provided."""
+synthetic generator of SURVEY.md 8(d) (the shipped sample volumes are Git-LFS stubs).  Without a
+transform list the pure index-math RandomCrop to PatchShape is applied; with one (transforms.py),
+the case's voxel spacing travels with the sample, which is what `Resample` reads."""
 import os
 import struct
 
@@ -133,6 +133,10 @@ class VolumeDataset(object):
         # the reference's per-sample transform list (vnet_tensorflow_amd.transforms.build_pipeline of TrainingSetting.Pipeline);
         # None = zero-pad + uniform RandomCrop to PatchShape
         self.transforms = transforms
+        if any(getattr(t, "device", None) is not None for t in (transforms or ())):
+            # batches are made on loader threads while the main thread may be capturing or replaying the step's hipGraph: a launch
+            # from another thread can invalidate the capture
+            raise ValueError("VolumeDataset runs its transforms on loader threads: they take the NumPy backend (device=None)")
         # volumes kept in host memory after the first load (synthetic cases are a pure function of their seed;
         # regenerating a 128^3 case costs ~0.3 s, 10x a training step)
         self.cache = {} if (cache if cache is not None else synthetic is not None) else None
@@ -155,7 +159,7 @@ class VolumeDataset(object):
             return len(self.cases) // self.batch
         return len(self.cases) // (self.world * self.batch)
 
-    def _load(self, case):
+    def _load(self, case, keep=True):
         if self.cache is not None and case in self.cache:
             return self.cache[case]
         if self.synthetic is not None:
@@ -165,8 +169,29 @@ class VolumeDataset(object):
         else:
             chans = [np.asarray(load_volume(os.path.join(case, f)), dtype=np.float32) for f in self.image_filenames]
             out = np.stack(chans, axis=-1), remap_labels(load_volume(os.path.join(case, self.label_filename)), self.classes)
-        if self.cache is not None:
+        if self.cache is not None and keep:
             self.cache[case] = out
+        return out
+
+    def _spacing(self, case):
+        if self.synthetic is not None:
+            return tuple(float(v) for v in self.synthetic.get("Spacing", (1.0, 1.0, 1.0)))
+        return volume_spacing(os.path.join(case, self.image_filenames[0]))
+
+    def _prepared(self, case):
+        """(sample, n): the case after the first n transforms.  With the cache on, n is the pipeline's deterministic prefix -- every
+        transform before the first one that draws from the generator (normalisation, Resample, Padding) -- and the result is what
+        is cached, so the resampling of a case is paid once, not once per visit; without a cache n = 0."""
+        from .transforms import deterministic_prefix, run_pipeline
+        key = ("prepared", case)
+        if self.cache is not None and key in self.cache:
+            return self.cache[key]
+        image, label = self._load(case, keep=False)
+        sample = {'image': image, 'label': label, 'spacing': self._spacing(case)}
+        n = deterministic_prefix(self.transforms) if self.cache is not None else 0
+        out = run_pipeline(self.transforms[:n], sample, None), n
+        if self.cache is not None:
+            self.cache[key] = out
         return out
 
     def epoch_plan(self):
@@ -194,14 +219,16 @@ class VolumeDataset(object):
         crop is then the ONLY copy between the cached volume and the DMA source); None: new arrays."""
         imgs, labs = [], []
         for i, (case, sd) in enumerate(zip(cases, seeds)):
-            image, label = self._load(case)
             if self.transforms is not None:
-                from .transforms import apply_pipeline
-                image, label = apply_pipeline(self.transforms, image, label, np.random.default_rng(sd))
+                from .transforms import run_pipeline
+                sample, n = self._prepared(case)
+                sample = run_pipeline(self.transforms[n:], sample, np.random.default_rng(sd))
+                image, label = sample['image'], sample['label']
                 if tuple(label.shape) != self.patch:
                     raise ValueError("the transform pipeline produced a %s sample, PatchShape is %s (end it with a crop to "
                                      "PatchShape, like the reference's pipeline3D.yaml)" % (tuple(label.shape), self.patch))
             else:
+                image, label = self._load(case)
                 image, label = random_crop(image, label, self.patch, np.random.default_rng(sd))
             if out is not None:
                 np.copyto(out[0][i], image, casting="unsafe")

@@ -6,8 +6,8 @@ What is carried over: the graph of model.py:428-568 (network, softmax, one-hot, 
 switch, argmax), the optimiser/LR schedule of model.py:641-666, the step loop of model.py:716-810
 (feed images/labels, dropout from config, batch-statistics BN, one optimiser step, print loss,
 checkpoint cadence, periodic test batch) and the sliding-window inference of model.py:866-937.
-What is not: SimpleITK I/O + resampling transforms, TensorBoard summaries,
-the 2-D path, UNet.  `sess` is accepted and ignored.
+What is not: SimpleITK I/O, its transforms other than `Resample`, TensorBoard
+summaries, the 2-D path.  `sess` is accepted and ignored.
 """
 import datetime
 import math
@@ -805,10 +805,11 @@ class image2label(object):
     def _dataset(self, data_dir, train):
         tf = None
         if self.training_pipeline:
-            # TrainingSetting.Pipeline: the reference's transform YAML (model.py:340-372); the index / intensity transforms
-            # are restated on arrays (vnet_tensorflow_amd/transforms.py), SimpleITK resampling ones are refused
+            # TrainingSetting.Pipeline: the reference's transform YAML (model.py:340-372); the index / intensity transforms and
+            # Resample are restated on arrays (vnet_tensorflow_amd/transforms.py; NumPy backend: batches are made on loader
+            # threads), the other SimpleITK ones are refused
             from . import transforms as vtf
-            tf = vtf.build_pipeline(self.training_pipeline, "train" if train else "test")
+            tf = vtf.build_pipeline(self.training_pipeline, "train" if train else "test", geometry=True)
         return vdata.VolumeDataset(data_dir, self.image_filenames, self.label_filename, self.label_classes,
                                    self.patch_shape, self.batch_size, train=train, synthetic=self.synthetic,
                                    rank=self.rank, world=self.world, transforms=tf)
@@ -929,12 +930,15 @@ class image2label(object):
         with torch.no_grad():
             return self.forward(batch, None, 0.0)[2]
 
-    # -- reference model.py:817-977 (array in / arrays out; SimpleITK resampling not carried) -----------------
+    # -- reference model.py:817-977 (array in / arrays out) ----------------------------------------------------------
     @in_context
-    def evaluate_single_3D(self, images_np):
+    def evaluate_single_3D(self, images_np, back_size=None, back_ratio=None):
         """images_np float32 [X,Y,Z,Cin] -> (label int64 [X,Y,Z], softmax float32 [K,X,Y,Z]).
         Patch enumeration, the duplicated last batch and argmax-of-summed-softmax follow
-        model.py:866-937 exactly; accumulation runs on the GPU."""
+        model.py:866-937 exactly; accumulation runs on the GPU.
+        back_size, back_ratio: the way back of model.py:939-975 -- the results are resampled ON THE DEVICE from images_np's grid to
+        a grid of back_size voxels whose spacing is back_ratio times this one's (label: nearest neighbour; probabilities: linear,
+        dividing the summed softmax by the count map tap by tap), and only they cross PCIe."""
         ps, st = list(self.patch_shape), list(self.evaluate_stride)
         pads = [(0, max(p - s, 0)) for s, p in zip(images_np.shape[:3], ps)]
         orig = images_np.shape[:3]
@@ -986,6 +990,13 @@ class image2label(object):
                 for j, idx in enumerate(bd['indexes']):
                     ops.accumulate_patch(sm[j], vol, cnt, (idx[0], idx[2], idx[4]))
                 feeder.step_done()
+        if back_size is not None:
+            label = ops.resample(torch.argmax(vol, dim=-1).to(torch.int32), back_size, back_ratio, "nearest")
+            label_np = label.cpu().numpy().astype(np.int64)
+            if not self.evaluate_probability_output:
+                return label_np, None
+            prob = ops.resample(vol, back_size, back_ratio, "linear", divisor=cnt)
+            return label_np, np.moveaxis(prob.cpu().numpy(), -1, 0)
         # argmax of the summed softmax (model.py:934) on the device: only the label map crosses PCIe unless probabilities are wanted
         label_np = torch.argmax(vol, dim=-1).to(torch.int16 if K < 32768 else torch.int64).cpu().numpy().astype(np.int64)
         sl = tuple(slice(0, s) for s in orig)
@@ -1003,24 +1014,39 @@ class image2label(object):
         self.build_model_graph()
         self._print("{}: Restoring checkpoint {}".format(_now(), self.checkpoint_path))
         self.load_checkpoint(self.checkpoint_path, with_optimizer=False)
+        tf, regrid = None, False
+        if self.evaluate_pipeline:
+            # EvaluationSetting.Pipeline: the 'evaluate' transform list of the reference's YAML (model.py:1142-1167).  Resample
+            # runs on the device here (this is the main thread and no stream capture is active); the other physical-grid
+            # transforms are refused
+            from . import resample as vrs
+            from . import transforms as vtf
+            tf = vtf.build_pipeline(self.evaluate_pipeline, "evaluate", geometry=True)
+            for t in tf:
+                if isinstance(t, vtf.Resample):
+                    t.device, regrid = self.device, True
         for case in sorted(os.listdir(self.evaluate_data_dir)):
             cdir = os.path.join(self.evaluate_data_dir, case)
             if not os.path.isdir(cdir):
                 continue
             chans = [np.asarray(vdata.load_volume(os.path.join(cdir, f)), dtype=np.float32) for f in self.evaluate_image_filenames]
             image = np.stack(chans, axis=-1)
-            if self.evaluate_pipeline:
-                # EvaluationSetting.Pipeline: the 'evaluate' transform list of the reference's YAML (model.py:1142-1167);
-                # intensity transforms and Padding are restated on arrays, physical-grid resampling is refused
-                from . import transforms as vtf
-                tf = vtf.build_pipeline(self.evaluate_pipeline, "evaluate")
-                image, _ = vtf.apply_pipeline(tf, image, np.zeros(image.shape[:3], dtype=np.int32), np.random.default_rng(0))
-            label, softmax = self.evaluate_single_3D(image)
-            label = label[tuple(slice(0, n) for n in chans[0].shape)]
-            if softmax is not None:
-                softmax = softmax[(slice(None),) + tuple(slice(0, n) for n in chans[0].shape)]
             # physical voxel size of the input (the reference compares GetPhysicalSize against VolumeThreshold, model.py:117-140)
             spacing = vdata.volume_spacing(os.path.join(cdir, self.evaluate_image_filenames[0]))
+            if regrid:
+                # the pipeline changes the grid: window on the transformed grid, then back to the input file's size and spacing
+                # (model.py:939-975) before the label filters below, which work in the input's physical units
+                sample = vtf.run_pipeline(tf, {'image': image, 'label': np.zeros(image.shape[:3], dtype=np.int32), 'spacing': spacing},
+                                          np.random.default_rng(0))
+                label, softmax = self.evaluate_single_3D(sample['image'], back_size=chans[0].shape,
+                                                         back_ratio=vrs.ratios(sample['spacing'], spacing))
+            else:
+                if tf is not None:
+                    image, _ = vtf.apply_pipeline(tf, image, np.zeros(image.shape[:3], dtype=np.int32), np.random.default_rng(0))
+                label, softmax = self.evaluate_single_3D(image)
+                label = label[tuple(slice(0, n) for n in chans[0].shape)]
+                if softmax is not None:
+                    softmax = softmax[(slice(None),) + tuple(slice(0, n) for n in chans[0].shape)]
             if self.evaluate_lcc:                                     # model.py:1218-1219
                 label = ExtractLargestConnectedComponents(label, spacing)
             if self.evaluate_volume_threshold and self.evaluate_volume_threshold > 0:      # model.py:1222-1223

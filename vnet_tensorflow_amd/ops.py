@@ -1585,6 +1585,44 @@ def max_pool2(x):
     return _MaxPool2Fn.apply(x)
 
 
+# ---- resampling onto a grid of another voxel spacing (include/vnet_hip_resample.h; rules: vnet_tensorflow_amd/resample.py) -----
+def resample(x, out_size, ratio, mode="linear", divisor=None):
+    """The reference's `Resample` geometry on device tensors, no autograd: output index i_a reads x at the continuous index
+    i_a * ratio[a] (ratio = output spacing / source spacing, doubles); samples at or past n_a - 0.5 are 0.
+    mode "linear": x float32 [X,Y,Z,C] or [X,Y,Z] -> float32 out_size (+ C); divisor float32 [X,Y,Z]: every tap is x / divisor in
+    double (0 where the divisor is 0) -- the sliding window's count map.  mode "nearest": x int32 [X,Y,Z] -> int32 out_size."""
+    if mode not in ("linear", "nearest"):
+        raise ValueError("resample: mode %r (linear | nearest)" % (mode,))
+    out_size, ratio = tuple(int(v) for v in out_size), tuple(float(v) for v in ratio)
+    if len(out_size) != 3 or len(ratio) != 3:
+        raise ValueError("resample: out_size and ratio take three values each")
+    if x.dim() not in ((3,) if mode == "nearest" else (3, 4)):
+        raise VnetHipError("resample: %s takes %s, got a %d-d tensor" % (mode, "[X,Y,Z]" if mode == "nearest" else "[X,Y,Z] or [X,Y,Z,C]", x.dim()))
+    if divisor is not None and (mode != "linear" or tuple(divisor.shape) != tuple(x.shape[:3])):
+        raise VnetHipError("resample: the divisor goes with mode 'linear' and has the shape of x's voxels")
+    shape = out_size + tuple(x.shape[3:])
+    if _meta(x):
+        return torch.empty(shape, dtype=x.dtype, device="meta")
+    if not x.is_cuda or (divisor is not None and not divisor.is_cuda):
+        raise VnetHipError("resample: tensor on %s -- the HIP library is the only compute path (no CPU fallback)" % (x.device,))
+    want = torch.float32 if mode == "linear" else torch.int32
+    if x.dtype != want or (divisor is not None and divisor.dtype != torch.float32):
+        raise VnetHipError("resample: mode %r expects %s, got %s" % (mode, want, x.dtype))
+    L = _lib.lib()
+    x = x.contiguous()
+    X, Y, Z = (int(v) for v in x.shape[:3])
+    y = torch.empty(shape, dtype=want, device=x.device)
+    if mode == "nearest":
+        with _Timed("resample nearest %dx%dx%d" % out_size, 0.0, 8.0 * y.numel()):
+            check(L.vnet_resample_nearest_i32(_ptr(x), _ptr(y), X, Y, Z, *out_size, *ratio, _stream()), "vnet_resample_nearest_i32")
+        return y
+    C = int(x.shape[3]) if x.dim() == 4 else 1
+    dv = divisor.contiguous() if divisor is not None else None
+    with _Timed("resample linear %dx%dx%d %d" % (out_size + (C,)), 0.0, 4.0 * (x.numel() + y.numel() + (dv.numel() if dv is not None else 0))):
+        check(L.vnet_resample_linear(_ptr(x), _ptr(dv), _ptr(y), C, X, Y, Z, *out_size, *ratio, _stream()), "vnet_resample_linear")
+    return y
+
+
 # ---- stand-alone activation (API parity with layers2.prelu; the networks use the fused bn_act) ------------
 class _ActFn(torch.autograd.Function):
     @staticmethod

@@ -5,17 +5,20 @@
     ExtremumNormalization     NiftiDataset3D.py:256-283      Normalization        NiftiDataset3D.py:167-185
     RandomFlip                NiftiDataset3D.py:187-208      Padding              NiftiDataset3D.py:400-456
     RandomCrop                NiftiDataset3D.py:458-551      RandomNoise          NiftiDataset3D.py:553-572
-    ConfidenceCrop2           NiftiDataset3D.py:661-793
+    ConfidenceCrop2           NiftiDataset3D.py:661-793      Resample             NiftiDataset3D.py:345-398
 
 A sample is {'image': float32 [X,Y,Z,C] (the reference keeps a list of C SimpleITK images), 'label': int [X,Y,Z]}; every
 transform is `t(sample, rng)` with an explicit numpy Generator (the reference draws from the global `random` / `np.random`
 state).  `build_pipeline` reads the reference's YAML schema (pipeline/pipeline3D.yaml: preprocess -> train|test|evaluate ->
-3D -> [{name, variables}], model.py:340-372) and instantiates by class name exactly like model.py:350.  Transforms that
-RESAMPLE on a physical grid (Resample, Reorient, Invert, BSplineDeformation, ConfidenceCrop) need SimpleITK's geometry and
-are out of scope: naming one raises."""
+3D -> [{name, variables}], model.py:340-372) and instantiates by class name exactly like model.py:350.  `Resample` changes the
+grid: the sample then carries its voxel spacing under 'spacing' (apply_pipeline / run_pipeline keep it alongside the sample through
+the transforms that know nothing of it), and build_pipeline instantiates it only when asked to (geometry=True).  The other
+transforms that need SimpleITK's geometry (Reorient, Invert, BSplineDeformation, ConfidenceCrop) are out of scope:
+naming one raises."""
 import numpy as np
 
-_SITK_ONLY = ("Resample", "Reorient", "Invert", "BSplineDeformation", "ConfidenceCrop")
+_SITK_ONLY = ("Reorient", "Invert", "BSplineDeformation", "ConfidenceCrop")
+_GEOMETRY = ("Resample",)
 
 
 def _size3(v, what):
@@ -239,12 +242,49 @@ class ConfidenceCrop2(object):
         return {'image': image, 'label': label}
 
 
+class Resample(object):
+    """Resample image (linear, every channel) and label (nearest neighbour) to `voxel_size` on a grid with the input's origin and
+    direction: n' = int(ceil(s * n / s')) voxels per axis, samples past the input are 0 (vnet_tensorflow_amd/resample.py states the
+    rules).  The sample's voxel spacing is sample['spacing'] ((1, 1, 1) when absent); the result carries the new one.
+    device: None = NumPy (the only backend a loader thread may use: a launch from another thread can invalidate the training
+    loop's stream capture); a torch device = upload, ops.resample, download."""
+
+    def __init__(self, voxel_size, device=None):
+        self.name = 'Resample'
+        assert isinstance(voxel_size, (float, tuple, list))
+        if isinstance(voxel_size, float):
+            self.voxel_size = (voxel_size, voxel_size, voxel_size)
+        else:
+            assert len(voxel_size) == 3
+            self.voxel_size = tuple(float(v) for v in voxel_size)
+        self.device = device
+
+    def __call__(self, sample, rng=None):
+        from . import resample as R
+        image, label = sample['image'], sample['label']
+        spacing = tuple(float(v) for v in sample.get('spacing', (1.0, 1.0, 1.0)))
+        size, ratio = R.output_size(label.shape, spacing, self.voxel_size), R.ratios(spacing, self.voxel_size)
+        if self.device is None:
+            image, label = R.linear(image, size, ratio), R.nearest(label, size, ratio)
+        else:
+            import torch
+            from . import ops
+            img = ops.resample(torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(self.device), size, ratio, "linear")
+            lab = ops.resample(torch.from_numpy(np.ascontiguousarray(label, dtype=np.int32)).to(self.device), size, ratio, "nearest")
+            image, label = img.cpu().numpy(), lab.cpu().numpy().astype(label.dtype, copy=False)
+        return {'image': image, 'label': label, 'spacing': self.voxel_size}
+
+
 _REGISTRY = {c.__name__: c for c in (Normalization, StatisticalNormalization, ExtremumNormalization, ManualNormalization,
-                                     RandomFlip, Padding, RandomCrop, RandomNoise, ConfidenceCrop2)}
+                                     RandomFlip, Padding, RandomCrop, RandomNoise, ConfidenceCrop2, Resample)}
+# transforms that draw from `rng`: everything in front of the first one is a pure function of the case (deterministic_prefix)
+_RANDOM = (RandomFlip, RandomCrop, RandomNoise, ConfidenceCrop2)
 
 
-def build_pipeline(yaml_path, phase):
-    """[transform] of preprocess -> `phase` ('train' | 'test' | 'evaluate') -> 3D of a reference pipeline YAML."""
+def build_pipeline(yaml_path, phase, geometry=False):
+    """[transform] of preprocess -> `phase` ('train' | 'test' | 'evaluate') -> 3D of a reference pipeline YAML.
+    geometry: instantiate `Resample` (the caller then passes each volume's voxel spacing to apply_pipeline / run_pipeline);
+    False keeps refusing it by name, like the transforms that stay out of scope."""
     import yaml
     with open(yaml_path) as f:
         spec = yaml.load(f, Loader=yaml.SafeLoader)
@@ -252,7 +292,7 @@ def build_pipeline(yaml_path, phase):
     out = []
     for t in entries:
         name = t["name"]
-        if name in _SITK_ONLY:
+        if name in _SITK_ONLY or (name in _GEOMETRY and not geometry):
             raise NotImplementedError("transform %r resamples on the physical grid and needs SimpleITK (out of scope here); "
                                       "resample the volumes offline and drop it from the pipeline" % name)
         if name not in _REGISTRY:
@@ -261,8 +301,27 @@ def build_pipeline(yaml_path, phase):
     return out
 
 
-def apply_pipeline(transforms, image, label, rng):
-    sample = {'image': image, 'label': label}
+def deterministic_prefix(transforms):
+    """Number of leading transforms that never draw from `rng`: their result is the same for every visit of a case."""
+    n = 0
+    while n < len(transforms) and not isinstance(transforms[n], _RANDOM):
+        n += 1
+    return n
+
+
+def run_pipeline(transforms, sample, rng):
+    """The sample after every transform, its voxel spacing under 'spacing' ((1, 1, 1) when the sample came without): the spacing is
+    carried past the transforms that return image and label alone (they keep the grid's spacing: crops and Padding keep origin-side
+    voxels and their size)."""
+    spacing = tuple(sample.get('spacing', (1.0, 1.0, 1.0)))
+    sample = dict(sample, spacing=spacing)
     for t in transforms:
-        sample = t(sample, rng)
+        out = t(sample, rng)
+        spacing = tuple(out.get('spacing', spacing))
+        sample = dict(out, spacing=spacing)
+    return sample
+
+
+def apply_pipeline(transforms, image, label, rng, spacing=(1, 1, 1)):
+    sample = run_pipeline(transforms, {'image': image, 'label': label, 'spacing': spacing}, rng)
     return sample['image'], sample['label']
