@@ -1,5 +1,5 @@
 """ctypes binding of libvnet_hip.so (include/vnet_hip.h, include/vnet_hip_unet.h, include/vnet_hip_head.h,
-include/vnet_hip_resample.h).
+include/vnet_hip_resample.h, include/vnet_hip_components.h).
 
 The library is the product: there is NO fallback.  If the shared object is missing, or a
 kernel reports an error, this module raises -- nothing silently routes to PyTorch or the CPU.
@@ -149,6 +149,14 @@ SIGNATURES_RESAMPLE = {
     "vnet_resample_nearest_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, _d, _vp]),
 }
 
+# fifth public header, include/vnet_hip_components.h (connected components and the two label filters of evaluate), same library
+SIGNATURES_COMPONENTS = {
+    "vnet_cc_ws_bytes": (_sz, [_i, _i, _i]),
+    "vnet_cc_roots": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "vnet_cc_largest": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp]),
+    "vnet_cc_volume_threshold": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _vp, _sz, _vp]),
+}
+
 
 class WgradJob(ctypes.Structure):
     """include/vnet_hip.h: vnet_wgrad_job (one layer of vnet_conv_wgrad_b16_group)."""
@@ -206,10 +214,11 @@ def lib():
                 setattr(L, name, _memo(fn, (b"BF16_DEEP", b"BF16_DEEP_TARGET"), L))     # (the kernel choice follows these options)
             elif name.endswith("_ws_bytes") or name.endswith("_stats_rows") or name == "vnet_conv_stats_from_reduce" or name == "vnet_packed_weight_floats":
                 setattr(L, name, _memo(fn))    # pure size queries, asked before every launch: answer repeats from a dict
-        for name, (res, args) in list(SIGNATURES_UNET.items()) + list(SIGNATURES_HEAD.items()) + list(SIGNATURES_RESAMPLE.items()):
+        for name, (res, args) in list(SIGNATURES_UNET.items()) + list(SIGNATURES_HEAD.items()) + list(SIGNATURES_RESAMPLE.items()) + \
+                list(SIGNATURES_COMPONENTS.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
-            if name in ("vnet_bn_head_ok", "vnet_bn_head_stats_rows", "vnet_bn_head_ws_bytes"):
+            if name in ("vnet_bn_head_ok", "vnet_bn_head_stats_rows", "vnet_bn_head_ws_bytes", "vnet_cc_ws_bytes"):
                 setattr(L, name, _memo(fn))
         _lib = L
     return _lib

@@ -932,13 +932,27 @@ class image2label(object):
 
     # -- reference model.py:817-977 (array in / arrays out) ----------------------------------------------------------
     @in_context
-    def evaluate_single_3D(self, images_np, back_size=None, back_ratio=None):
+    def evaluate_single_3D(self, images_np, back_size=None, back_ratio=None, largest_component=False, volume_threshold=None,
+                           spacing=None, extent=None):
         """images_np float32 [X,Y,Z,Cin] -> (label int64 [X,Y,Z], softmax float32 [K,X,Y,Z]).
         Patch enumeration, the duplicated last batch and argmax-of-summed-softmax follow
         model.py:866-937 exactly; accumulation runs on the GPU.
         back_size, back_ratio: the way back of model.py:939-975 -- the results are resampled ON THE DEVICE from images_np's grid to
         a grid of back_size voxels whose spacing is back_ratio times this one's (label: nearest neighbour; probabilities: linear,
-        dividing the summed softmax by the count map tap by tap), and only they cross PCIe."""
+        dividing the summed softmax by the count map tap by tap), and only they cross PCIe.
+        largest_component, volume_threshold (> 0), spacing: the label filters of model.py:1218-1223 ON THE DEVICE, before the label
+        is copied out -- the largest face-connected component first, then the threshold on its 0/1 result, `spacing` the voxel size
+        of the grid the label is returned on.  They see the volume the caller gets: on the back_size branch the resampled label, else
+        the label cropped to images_np's extent, and to `extent` where that is smaller (evaluate(): the input file's size, which a
+        Padding transform may have grown).  The label is then the 0/1 map.  With neither filter nothing changes."""
+        vt = volume_threshold if volume_threshold is not None and volume_threshold > 0 else None
+        filtered = bool(largest_component) or vt is not None
+        sp = tuple(float(v) for v in spacing) if spacing is not None else (1.0, 1.0, 1.0)
+
+        def filters(label):
+            if largest_component:
+                return ops.largest_component(label, classes=self.output_channel_num, min_volume=vt, spacing=sp)
+            return ops.volume_threshold(label, vt, sp)
         ps, st = list(self.patch_shape), list(self.evaluate_stride)
         pads = [(0, max(p - s, 0)) for s, p in zip(images_np.shape[:3], ps)]
         orig = images_np.shape[:3]
@@ -992,14 +1006,24 @@ class image2label(object):
                 feeder.step_done()
         if back_size is not None:
             label = ops.resample(torch.argmax(vol, dim=-1).to(torch.int32), back_size, back_ratio, "nearest")
+            if filtered:
+                label = filters(label)
             label_np = label.cpu().numpy().astype(np.int64)
             if not self.evaluate_probability_output:
                 return label_np, None
             prob = ops.resample(vol, back_size, back_ratio, "linear", divisor=cnt)
             return label_np, np.moveaxis(prob.cpu().numpy(), -1, 0)
         # argmax of the summed softmax (model.py:934) on the device: only the label map crosses PCIe unless probabilities are wanted
-        label_np = torch.argmax(vol, dim=-1).to(torch.int16 if K < 32768 else torch.int64).cpu().numpy().astype(np.int64)
         sl = tuple(slice(0, s) for s in orig)
+        if filtered:
+            # the filters must see the cropped volume, not the window padding: crop on the device, filter, copy the 0/1 map out
+            fl = tuple(slice(0, min(s, e)) for s, e in zip(orig, extent if extent is not None else orig))
+            label_np = filters(torch.argmax(vol, dim=-1)[fl].to(torch.int32)).cpu().numpy().astype(np.int64)
+            if not self.evaluate_probability_output:
+                return label_np, None
+            vol_np, cnt_np = vol.cpu().numpy(), cnt.cpu().numpy()
+            return label_np, (np.moveaxis(vol_np, -1, 0) / np.float32(cnt_np))[(slice(None),) + sl]
+        label_np = torch.argmax(vol, dim=-1).to(torch.int16 if K < 32768 else torch.int64).cpu().numpy().astype(np.int64)
         if not self.evaluate_probability_output:
             return label_np[sl], None
         vol_np, cnt_np = vol.cpu().numpy(), cnt.cpu().numpy()
@@ -1033,24 +1057,26 @@ class image2label(object):
             image = np.stack(chans, axis=-1)
             # physical voxel size of the input (the reference compares GetPhysicalSize against VolumeThreshold, model.py:117-140)
             spacing = vdata.volume_spacing(os.path.join(cdir, self.evaluate_image_filenames[0]))
+            vt = self.evaluate_volume_threshold if self.evaluate_volume_threshold and self.evaluate_volume_threshold > 0 else None
+            on_device = {}
+            if self.evaluate_lcc or vt is not None:
+                on_device = dict(largest_component=bool(self.evaluate_lcc), volume_threshold=vt, spacing=spacing, extent=chans[0].shape)
             if regrid:
                 # the pipeline changes the grid: window on the transformed grid, then back to the input file's size and spacing
                 # (model.py:939-975) before the label filters below, which work in the input's physical units
                 sample = vtf.run_pipeline(tf, {'image': image, 'label': np.zeros(image.shape[:3], dtype=np.int32), 'spacing': spacing},
                                           np.random.default_rng(0))
                 label, softmax = self.evaluate_single_3D(sample['image'], back_size=chans[0].shape,
-                                                         back_ratio=vrs.ratios(sample['spacing'], spacing))
+                                                         back_ratio=vrs.ratios(sample['spacing'], spacing), **on_device)
             else:
                 if tf is not None:
                     image, _ = vtf.apply_pipeline(tf, image, np.zeros(image.shape[:3], dtype=np.int32), np.random.default_rng(0))
-                label, softmax = self.evaluate_single_3D(image)
+                label, softmax = self.evaluate_single_3D(image, **on_device)
                 label = label[tuple(slice(0, n) for n in chans[0].shape)]
                 if softmax is not None:
                     softmax = softmax[(slice(None),) + tuple(slice(0, n) for n in chans[0].shape)]
-            if self.evaluate_lcc:                                     # model.py:1218-1219
-                label = ExtractLargestConnectedComponents(label, spacing)
-            if self.evaluate_volume_threshold and self.evaluate_volume_threshold > 0:      # model.py:1222-1223
-                label = volume_threshold(label, self.evaluate_volume_threshold, spacing)
+            # the label filters (model.py:1218-1223: largest component, then the volume threshold) ran on the device, on the input's
+            # grid, before the label was copied out; the host functions above remain their statement and the route of ops' fallbacks
             out = os.path.join(cdir, self.evaluate_label_filename)
             if out.endswith(".npy"):
                 np.save(out, label.astype(np.int16))

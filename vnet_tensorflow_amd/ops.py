@@ -173,10 +173,10 @@ def use_step_state(state):
         _STEP_STATE["active"] = prev
 
 
-def _need_gpu(t, what, allow16=False):
+def _need_gpu(t, what, allow16=False, any_dtype=False):
     if not t.is_cuda:
         raise VnetHipError("%s: tensor on %s -- the HIP library is the only compute path (no CPU fallback)" % (what, t.device))
-    if t.dtype != torch.float32 and not (allow16 and t.dtype == torch.bfloat16):
+    if not any_dtype and t.dtype != torch.float32 and not (allow16 and t.dtype == torch.bfloat16):
         raise VnetHipError("%s: expected float32%s, got %s" % (what, " or bfloat16" if allow16 else "", t.dtype))
 
 
@@ -1621,6 +1621,86 @@ def resample(x, out_size, ratio, mode="linear", divisor=None):
     with _Timed("resample linear %dx%dx%d %d" % (out_size + (C,)), 0.0, 4.0 * (x.numel() + y.numel() + (dv.numel() if dv is not None else 0))):
         check(L.vnet_resample_linear(_ptr(x), _ptr(dv), _ptr(y), C, X, Y, Z, *out_size, *ratio, _stream()), "vnet_resample_linear")
     return y
+
+
+# ---- connected components and the two label filters of evaluate (include/vnet_hip_components.h) -------------------------------
+def _cc_label(label, what):
+    """The label map as the kernels take it: int32 [X,Y,Z], contiguous.  Foreground is label != 0 whatever the class, so a map of another
+    dtype goes in as its 0/1 mask (exact for every dtype; a cast of the values could wrap a class to 0)."""
+    if label.dim() != 3 or label.numel() == 0:
+        raise VnetHipError("%s: takes a non-empty [X,Y,Z] label map, got %s" % (what, tuple(label.shape)))
+    _need_gpu(label, what, any_dtype=True)
+    return (label if label.dtype == torch.int32 else (label != 0).to(torch.int32)).contiguous()
+
+
+def _cc_host(label, fn, *args):
+    """The host function of model.py on a device label map (the route of volumes the kernels' int32 index cannot hold, and of class
+    counts past the reference's uint8 cast); the 0/1 result goes back to the label's device."""
+    return torch.from_numpy(fn(label.cpu().numpy(), *args)).to(label.device)
+
+
+def _voxel_volume(spacing):
+    import numpy as np
+    return float(np.prod(spacing))                   # the double the host function forms (model.volume_threshold)
+
+
+def component_roots(label, sizes=False):
+    """Face-connected (6 neighbours) components of label != 0, all non-zero classes one mask: int32 [X,Y,Z], every foreground voxel
+    holds its component's smallest linear index, the background -1.  sizes=True: also int32 [X,Y,Z] with the component's voxel
+    count at its representative and 0 elsewhere."""
+    x = _cc_label(label, "component_roots")
+    X, Y, Z = (int(v) for v in x.shape)
+    roots = torch.empty((X, Y, Z), dtype=torch.int32, device=x.device)
+    cnt = torch.empty((X, Y, Z), dtype=torch.int32, device=x.device) if sizes else None
+    with _Timed("cc roots %dx%dx%d" % (X, Y, Z), 0.0, 4.0 * x.numel() * (4 if sizes else 3)):
+        check(_lib.lib().vnet_cc_roots(_ptr(x), _ptr(roots), _ptr(cnt), X, Y, Z, _stream()), "vnet_cc_roots")
+    return (roots, cnt) if sizes else roots
+
+
+def _cc_filter(x, entry, *args):
+    L = _lib.lib()
+    X, Y, Z = (int(v) for v in x.shape)
+    need = L.vnet_cc_ws_bytes(X, Y, Z)
+    if need == 0:
+        return None                                  # more voxels than an int32 indexes: the caller takes the host function
+    fn = getattr(L, entry)
+    out = torch.empty((X, Y, Z), dtype=torch.uint8, device=x.device)
+    ws = workspace(need, x.device)
+    with _Timed("%s %dx%dx%d" % (entry[5:], X, Y, Z), 0.0, 25.0 * x.numel()):
+        check(fn(_ptr(x), _ptr(out), X, Y, Z, *args, _ptr(ws), need, _stream()), entry)
+    return out
+
+
+def largest_component(label, classes=None, min_volume=None, spacing=(1.0, 1.0, 1.0)):
+    """model.ExtractLargestConnectedComponents on a device label map: uint8 [X,Y,Z], 1 on the face-connected component of label != 0
+    with the most voxels (of equal counts the one whose first voxel comes first in C order), 0 elsewhere.
+    min_volume: model.volume_threshold(result, min_volume, spacing) applied as well -- the result is one component, so it stays iff
+    count * prod(spacing) > min_volume.
+    classes: the number of classes K (labels in [0, K)).  The reference casts the label to uint8 first; for K <= 255 that changes
+    nothing, a larger K takes the host function.  Not given: the label's range is read back from the device to decide."""
+    from . import model as _model
+    x = _cc_label(label, "largest_component")
+    if classes is None:
+        lo, hi = (int(v) for v in torch.aminmax(label))
+        classes = 256 if (lo < -255 or hi > 255) else 2
+    out = None
+    if int(classes) <= 255:
+        out = _cc_filter(x, "vnet_cc_largest", int(min_volume is not None), float(min_volume) if min_volume is not None else 0.0,
+                         _voxel_volume(spacing) if min_volume is not None else 1.0)
+    if out is None:
+        out = _cc_host(label, _model.ExtractLargestConnectedComponents, spacing)
+        if min_volume is not None:
+            out = _cc_host(out, _model.volume_threshold, min_volume, spacing)
+    return out
+
+
+def volume_threshold(label, volume, spacing=(1.0, 1.0, 1.0)):
+    """model.volume_threshold on a device label map: uint8 [X,Y,Z], 1 on every face-connected component of label != 0 whose voxel
+    count times prod(spacing) exceeds `volume` (compared in double, strictly), 0 elsewhere."""
+    from . import model as _model
+    x = _cc_label(label, "volume_threshold")
+    out = _cc_filter(x, "vnet_cc_volume_threshold", float(volume), _voxel_volume(spacing))
+    return out if out is not None else _cc_host(label, _model.volume_threshold, volume, spacing)
 
 
 # ---- stand-alone activation (API parity with layers2.prelu; the networks use the fused bn_act) ------------
