@@ -1,5 +1,5 @@
 """ctypes binding of libvnet_hip.so (include/vnet_hip.h, include/vnet_hip_unet.h, include/vnet_hip_head.h,
-include/vnet_hip_resample.h, include/vnet_hip_components.h).
+include/vnet_hip_resample.h, include/vnet_hip_components.h, include/vnet_hip_deform.h).
 
 The library is the product: there is NO fallback.  If the shared object is missing, or a
 kernel reports an error, this module raises -- nothing silently routes to PyTorch or the CPU.
@@ -157,6 +157,12 @@ SIGNATURES_COMPONENTS = {
     "vnet_cc_volume_threshold": (_i, [_vp, _vp, _i, _i, _i, _d, _d, _vp, _sz, _vp]),
 }
 
+# sixth public header, include/vnet_hip_deform.h (the BSplineDeformation augmentation), same library
+SIGNATURES_DEFORM = {
+    "vnet_bspline_deform_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _d, _d, _d, _vp]),
+    "vnet_bspline_deform_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _d, _d, _d, _vp]),
+}
+
 
 class WgradJob(ctypes.Structure):
     """include/vnet_hip.h: vnet_wgrad_job (one layer of vnet_conv_wgrad_b16_group)."""
@@ -215,7 +221,7 @@ def lib():
             elif name.endswith("_ws_bytes") or name.endswith("_stats_rows") or name == "vnet_conv_stats_from_reduce" or name == "vnet_packed_weight_floats":
                 setattr(L, name, _memo(fn))    # pure size queries, asked before every launch: answer repeats from a dict
         for name, (res, args) in list(SIGNATURES_UNET.items()) + list(SIGNATURES_HEAD.items()) + list(SIGNATURES_RESAMPLE.items()) + \
-                list(SIGNATURES_COMPONENTS.items()):
+                list(SIGNATURES_COMPONENTS.items()) + list(SIGNATURES_DEFORM.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
             if name in ("vnet_bn_head_ok", "vnet_bn_head_stats_rows", "vnet_bn_head_ws_bytes", "vnet_cc_ws_bytes"):

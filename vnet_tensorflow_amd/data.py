@@ -133,9 +133,10 @@ class VolumeDataset(object):
         # the reference's per-sample transform list (vnet_tensorflow_amd.transforms.build_pipeline of TrainingSetting.Pipeline);
         # None = zero-pad + uniform RandomCrop to PatchShape
         self.transforms = transforms
-        if any(getattr(t, "device", None) is not None for t in (transforms or ())):
+        if any(getattr(t, "device", None) is not None and not getattr(t, "loader_safe", False) for t in (transforms or ())):
             # batches are made on loader threads while the main thread may be capturing or replaying the step's hipGraph: a launch
-            # from another thread can invalidate the capture
+            # from another thread can invalidate the capture.  The exception is a transform that declares loader_safe: its device
+            # work runs inside ops.side_work (a lock the capture holds, a stream of the thread's own, synchronised before release)
             raise ValueError("VolumeDataset runs its transforms on loader threads: they take the NumPy backend (device=None)")
         # volumes kept in host memory after the first load (synthetic cases are a pure function of their seed;
         # regenerating a 128^3 case costs ~0.3 s, 10x a training step)

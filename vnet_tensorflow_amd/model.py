@@ -302,6 +302,7 @@ class image2label(object):
         self.loss_weights = T['Loss'].get('Weights', [])
         self.loss_alpha = T['Loss'].get('Alpha', 1)
         self.training_pipeline = T.get('Pipeline')
+        self.deform_on_device = bool(T.get('DeformOnDevice', False))
         E = self.config.get('EvaluationSetting', {})
         self.checkpoint_path = E.get('CheckpointPath')
         ED = E.get('Data', {})
@@ -574,7 +575,9 @@ class image2label(object):
         ops.set_param_grad_stream(False)
         ops.settle_pack_registry()
         try:
-            loss = self._capture_mode(mode, grads, update, grads_rest)
+            # (ops.side_work: while this lock is held no loader thread has device work in flight or can start any)
+            with ops.capture_lock():
+                loss = self._capture_mode(mode, grads, update, grads_rest)
         finally:
             ops.set_param_grad_stream(pg_on)
         self._g_loss = loss.detach()
@@ -807,9 +810,13 @@ class image2label(object):
         if self.training_pipeline:
             # TrainingSetting.Pipeline: the reference's transform YAML (model.py:340-372); the index / intensity transforms and
             # Resample are restated on arrays (vnet_tensorflow_amd/transforms.py; NumPy backend: batches are made on loader
-            # threads), the other SimpleITK ones are refused
+            # threads), BSplineDeformation too; the other SimpleITK ones are refused.  TrainingSetting.DeformOnDevice: true gives
+            # BSplineDeformation the model's device -- its kernel then runs from the loader threads inside ops.side_work.  Off by
+            # default until profiles/bench_deform.py has shown that the device path, copies included, beats the NumPy backend
             from . import transforms as vtf
-            tf = vtf.build_pipeline(self.training_pipeline, "train" if train else "test", geometry=True)
+            on_dev = bool(getattr(self, "deform_on_device", False)) and self.device.type == "cuda"
+            tf = vtf.build_pipeline(self.training_pipeline, "train" if train else "test", geometry=True, deformation=True,
+                                    device=self.device if on_dev else None)
         return vdata.VolumeDataset(data_dir, self.image_filenames, self.label_filename, self.label_classes,
                                    self.patch_shape, self.batch_size, train=train, synthetic=self.synthetic,
                                    rank=self.rank, world=self.world, transforms=tf)

@@ -10,6 +10,7 @@ import contextlib
 import ctypes
 import math
 import os as _os
+import threading
 import weakref
 
 import torch
@@ -1621,6 +1622,94 @@ def resample(x, out_size, ratio, mode="linear", divisor=None):
     with _Timed("resample linear %dx%dx%d %d" % (out_size + (C,)), 0.0, 4.0 * (x.numel() + y.numel() + (dv.numel() if dv is not None else 0))):
         check(L.vnet_resample_linear(_ptr(x), _ptr(dv), _ptr(y), C, X, Y, Z, *out_size, *ratio, _stream()), "vnet_resample_linear")
     return y
+
+
+# ---- free-form deformation (include/vnet_hip_deform.h; rules: vnet_tensorflow_amd/deform.py) ------------------------------------
+def bspline_deform(x, coef, spacing, kind="image"):
+    """The reference's `BSplineDeformation` on device tensors, no autograd: every voxel reads x at its own index plus the cubic B-spline
+    displacement of the 13^3 control grid `coef` (6591 doubles in ITK's layout; a float64 tensor on x's device, or anything
+    torch.as_tensor takes, which is then uploaded), linear interpolation, 0 outside.  kind "image": x float32 [X,Y,Z,C] or [X,Y,Z] ->
+    float32; kind "label": x int32 [X,Y,Z] -> int32, the blend truncated toward zero.  x keeps its storage when it is dense (a view
+    that starts off a 16-byte boundary takes the one-channel path).  Launches on torch's current stream of the calling thread."""
+    if kind not in ("image", "label"):
+        raise ValueError("bspline_deform: kind %r (image | label)" % (kind,))
+    spacing = tuple(float(v) for v in spacing)
+    if len(spacing) != 3:
+        raise ValueError("bspline_deform: spacing takes three values")
+    if x.dim() not in ((3,) if kind == "label" else (3, 4)):
+        raise VnetHipError("bspline_deform: %s takes %s, got a %d-d tensor" % (kind, "[X,Y,Z]" if kind == "label" else "[X,Y,Z] or [X,Y,Z,C]", x.dim()))
+    ncoef = int(coef.numel()) if isinstance(coef, torch.Tensor) else int(len(coef))
+    if ncoef != 3 * 13 ** 3:
+        raise ValueError("bspline_deform: the control grid has %d parameters, got %d" % (3 * 13 ** 3, ncoef))
+    if _meta(x):
+        return torch.empty(tuple(x.shape), dtype=x.dtype, device="meta")
+    if not x.is_cuda:
+        raise VnetHipError("bspline_deform: tensor on %s -- the HIP library is the only compute path (no CPU fallback)" % (x.device,))
+    want = torch.float32 if kind == "image" else torch.int32
+    if x.dtype != want:
+        raise VnetHipError("bspline_deform: kind %r expects %s, got %s" % (kind, want, x.dtype))
+    if not (isinstance(coef, torch.Tensor) and coef.device == x.device and coef.dtype == torch.float64):
+        coef = torch.as_tensor(coef, dtype=torch.float64).to(x.device)
+    L = _lib.lib()
+    x, coef = x.contiguous(), coef.contiguous()
+    X, Y, Z = (int(v) for v in x.shape[:3])
+    C = int(x.shape[3]) if x.dim() == 4 else 1
+    y = torch.empty(tuple(x.shape), dtype=want, device=x.device)
+    # torch's current stream of THIS thread, never the redirect of the parameter-gradient section (_LAUNCH_ON is process-wide and
+    # belongs to the training step; this op also runs on loader threads, inside side_work)
+    stream = torch._C._cuda_getCurrentRawStream(x.device.index if x.device.index is not None else torch._C._cuda_getDevice())
+    entry = "vnet_bspline_deform_f32" if kind == "image" else "vnet_bspline_deform_i32"
+    with _Timed("bspline_deform %s %dx%dx%d %d" % (kind, X, Y, Z, C), 0.0, 4.0 * (x.numel() + y.numel())):
+        check(getattr(L, entry)(_ptr(x), _ptr(y), X, Y, Z, C, _ptr(coef), *spacing, stream), entry)
+    return y
+
+
+# ---- device work of a thread other than the training loop's (loader threads) -----------------------------------------------------
+# The training step is captured into a hipGraph once and replayed; a launch, an allocation or a copy that another thread makes while
+# the capture is open can end up inside it or invalidate it.  side_work() is the one door for such threads: a process-wide lock that
+# model._build_step_graph holds around its capture, so nothing of a loader thread can fall inside a capture by construction; a
+# stream of the thread's own, so its work orders against nothing of the step's streams; and a synchronise of that stream alone
+# before the lock is released, so what the thread enqueued is finished -- its tensors can be freed and its pinned results read --
+# before a capture can begin.
+_SIDE_LOCK = threading.RLock()
+_SIDE_LOCAL = threading.local()
+
+
+def capture_lock():
+    """The lock of side_work(): hold it around a stream capture."""
+    return _SIDE_LOCK
+
+
+@contextlib.contextmanager
+def side_work(device):
+    """Inside: torch's current stream (of this thread) is this thread's side stream on `device`, and no stream capture of
+    model._build_step_graph is open or can begin.  Yields the stream.  On exit the stream is synchronised, then the lock released."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise VnetHipError("side_work: device %s -- the HIP library is the only compute path (no CPU fallback)" % (device,))
+    with _SIDE_LOCK:
+        streams = _SIDE_LOCAL.__dict__.setdefault("streams", {})
+        st = streams.get(device)
+        if st is None:
+            st = streams[device] = torch.cuda.Stream(device=device)
+        try:
+            with torch.cuda.stream(st):
+                yield st
+        finally:
+            st.synchronize()
+
+
+def pinned_staging(name, shape, dtype):
+    """A pinned host tensor of this thread, kept and reused under `name` (grown when a larger one is asked for): the source and the
+    destination of side_work's asynchronous copies.  Valid until the thread's next request under the same name."""
+    bufs = _SIDE_LOCAL.__dict__.setdefault("pinned", {})
+    n = 1
+    for v in shape:
+        n *= int(v)
+    buf = bufs.get((name, dtype))
+    if buf is None or buf.numel() < n:
+        buf = bufs[(name, dtype)] = torch.empty(max(n, 1), dtype=dtype, pin_memory=True)
+    return buf[:n].view(tuple(int(v) for v in shape))
 
 
 # ---- connected components and the two label filters of evaluate (include/vnet_hip_components.h) -------------------------------

@@ -6,19 +6,22 @@
     RandomFlip                NiftiDataset3D.py:187-208      Padding              NiftiDataset3D.py:400-456
     RandomCrop                NiftiDataset3D.py:458-551      RandomNoise          NiftiDataset3D.py:553-572
     ConfidenceCrop2           NiftiDataset3D.py:661-793      Resample             NiftiDataset3D.py:345-398
+    BSplineDeformation        NiftiDataset3D.py:795-832
 
 A sample is {'image': float32 [X,Y,Z,C] (the reference keeps a list of C SimpleITK images), 'label': int [X,Y,Z]}; every
 transform is `t(sample, rng)` with an explicit numpy Generator (the reference draws from the global `random` / `np.random`
 state).  `build_pipeline` reads the reference's YAML schema (pipeline/pipeline3D.yaml: preprocess -> train|test|evaluate ->
 3D -> [{name, variables}], model.py:340-372) and instantiates by class name exactly like model.py:350.  `Resample` changes the
 grid: the sample then carries its voxel spacing under 'spacing' (apply_pipeline / run_pipeline keep it alongside the sample through
-the transforms that know nothing of it), and build_pipeline instantiates it only when asked to (geometry=True).  The other
-transforms that need SimpleITK's geometry (Reorient, Invert, BSplineDeformation, ConfidenceCrop) are out of scope:
-naming one raises."""
+the transforms that know nothing of it), and build_pipeline instantiates it only when asked to (geometry=True).
+`BSplineDeformation` keeps the grid and resamples on it (vnet_tensorflow_amd/deform.py states the rules); build_pipeline instantiates
+it only when asked to (deformation=True).  The other transforms that need SimpleITK's geometry (Reorient, Invert, ConfidenceCrop) are
+out of scope: naming one raises."""
 import numpy as np
 
 _SITK_ONLY = ("Reorient", "Invert", "BSplineDeformation", "ConfidenceCrop")
 _GEOMETRY = ("Resample",)
+_DEFORMATION = ("BSplineDeformation",)       # (listed in _SITK_ONLY: refused unless build_pipeline is asked for it)
 
 
 def _size3(v, what):
@@ -275,16 +278,67 @@ class Resample(object):
         return {'image': image, 'label': label, 'spacing': self.voxel_size}
 
 
+class BSplineDeformation(object):
+    """Free-form deformation: image and label are resampled on their own grid through a cubic B-spline displacement field whose
+    3 * 13^3 control values are `rng.random(6591) * randomness` (the reference draws np.random.random); linear interpolation for the
+    image AND the label (the reference passes no interpolator), the label truncated to its integer type, samples from outside are 0
+    (vnet_tensorflow_amd/deform.py states the rules).  The grid is kept: the sample's 'spacing' ((1, 1, 1) when absent) is read and
+    passed through.
+    device: None = NumPy; a torch device = pinned staging, upload, ops.bspline_deform, download, all inside ops.side_work(device) --
+    which is what makes this transform safe on a loader thread (loader_safe) while the training loop captures or replays its graph."""
+    loader_safe = True
+
+    def __init__(self, randomness=10, device=None):
+        self.name = 'BSpline Deformation'
+        if not isinstance(randomness, (int, float)) or not randomness > 0:
+            raise RuntimeError('Randomness should be non zero values')
+        self.randomness = randomness
+        self.device = device
+
+    def __call__(self, sample, rng):
+        from . import deform as D
+        image, label = sample['image'], sample['label']
+        spacing = tuple(float(v) for v in sample.get('spacing', (1.0, 1.0, 1.0)))
+        coef = rng.random(D.PARAMS) * self.randomness
+        if self.device is None:
+            image, label = D.linear(image, coef, spacing), D.label(label, coef, spacing)
+        else:
+            image, label = self._on_device(image, label, coef, spacing)
+        return {'image': image, 'label': label, 'spacing': spacing}
+
+    def _on_device(self, image, label, coef, spacing):
+        import torch
+        from . import ops
+        if not np.issubdtype(label.dtype, np.integer) or label.dtype.itemsize > 4 or label.dtype == np.uint32:
+            raise ValueError("BSplineDeformation(device=...): the label map goes through int32, got %s" % (label.dtype,))
+        with ops.side_work(self.device) as stream:
+            hi = ops.pinned_staging("deform.image", image.shape, torch.float32)
+            hl = ops.pinned_staging("deform.label", label.shape, torch.int32)
+            hc = ops.pinned_staging("deform.coef", coef.shape, torch.float64)
+            np.copyto(hi.numpy(), image, casting="unsafe")
+            np.copyto(hl.numpy(), label, casting="unsafe")
+            np.copyto(hc.numpy(), coef)
+            di, dl, dc = (h.to(self.device, non_blocking=True) for h in (hi, hl, hc))
+            yi, yl = ops.bspline_deform(di, dc, spacing, "image"), ops.bspline_deform(dl, dc, spacing, "label")
+            hi.copy_(yi, non_blocking=True)
+            hl.copy_(yl, non_blocking=True)
+            stream.synchronize()
+            # (the staging buffers are this thread's and are reused by its next call: hand out copies)
+            return hi.numpy().copy(), hl.numpy().astype(label.dtype)
+
+
 _REGISTRY = {c.__name__: c for c in (Normalization, StatisticalNormalization, ExtremumNormalization, ManualNormalization,
-                                     RandomFlip, Padding, RandomCrop, RandomNoise, ConfidenceCrop2, Resample)}
+                                     RandomFlip, Padding, RandomCrop, RandomNoise, ConfidenceCrop2, Resample,
+                                     BSplineDeformation)}
 # transforms that draw from `rng`: everything in front of the first one is a pure function of the case (deterministic_prefix)
-_RANDOM = (RandomFlip, RandomCrop, RandomNoise, ConfidenceCrop2)
+_RANDOM = (RandomFlip, RandomCrop, RandomNoise, ConfidenceCrop2, BSplineDeformation)
 
 
-def build_pipeline(yaml_path, phase, geometry=False):
+def build_pipeline(yaml_path, phase, geometry=False, deformation=False, device=None):
     """[transform] of preprocess -> `phase` ('train' | 'test' | 'evaluate') -> 3D of a reference pipeline YAML.
     geometry: instantiate `Resample` (the caller then passes each volume's voxel spacing to apply_pipeline / run_pipeline);
-    False keeps refusing it by name, like the transforms that stay out of scope."""
+    False keeps refusing it by name, like the transforms that stay out of scope.
+    deformation: instantiate `BSplineDeformation` (False keeps refusing it by name), on `device` (None = NumPy)."""
     import yaml
     with open(yaml_path) as f:
         spec = yaml.load(f, Loader=yaml.SafeLoader)
@@ -292,12 +346,15 @@ def build_pipeline(yaml_path, phase, geometry=False):
     out = []
     for t in entries:
         name = t["name"]
-        if name in _SITK_ONLY or (name in _GEOMETRY and not geometry):
+        if (name in _SITK_ONLY and not (deformation and name in _DEFORMATION)) or (name in _GEOMETRY and not geometry):
             raise NotImplementedError("transform %r resamples on the physical grid and needs SimpleITK (out of scope here); "
                                       "resample the volumes offline and drop it from the pipeline" % name)
         if name not in _REGISTRY:
             raise AttributeError("module 'NiftiDataset3D' has no attribute %r" % name)
-        out.append(_REGISTRY[name](**(t.get("variables") or {})))
+        kw = dict(t.get("variables") or {})
+        if name in _DEFORMATION and device is not None:
+            kw["device"] = device
+        out.append(_REGISTRY[name](**kw))
     return out
 
 
