@@ -265,6 +265,11 @@ def test_bn_act_b16(dev, M, C, act, res, small, monkeypatch):
     monkeypatch.setitem(ops._SMALL_BN, "rows", 8192)          # (default 512: only where it measured faster)
     if small and int(np.prod(M)) > 8192:
         pytest.skip("more rows than the small-tensor kernels take")
+    _bn_act_b16_case(dev, M, C, act, res)
+
+
+def _bn_act_b16_case(dev, M, C, act, res):
+    from vnet_tensorflow_amd import ops
     rng = np.random.default_rng(C + len(M))
     shape = M + (C,)
     x = rb(rng.standard_normal(shape) * 2 + 0.5)

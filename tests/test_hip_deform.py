@@ -6,6 +6,8 @@ Bounds.  Image: |y - y64| <= 2^-23 max|x| + 6e-12 max|x| -- one rounding to floa
 at most 1e-12 voxels, times three axes, times a neighbour difference of at most 2 max|x|.  Label: equality.  A label depends on floor(c)
 and on a truncation, so a voxel whose source index lies within 1e-9 of an integer or of n - 0.5 is not decidable across summation
 orders: every case asserts that its seeded inputs have no such voxel (deform.undecidable), then demands equality everywhere."""
+import os
+import re
 import threading
 
 import numpy as np
@@ -20,8 +22,33 @@ SPACING = (1.0, 0.8, 1.25)
 # pass the kernel's grid cap of 4096 workgroups
 SMALL = [((13, 10, 7), 1, 0), ((13, 10, 7), 3, 0), ((12, 9, 8), 4, 0), ((12, 9, 8), 4, 1)]
 LARGE = [((128, 96, 96), 1, 0), ((192, 172, 16), 1, 0)]
-CASES = [(s, C, off, r) for s, C, off in SMALL for r in (1.5, 10)] + [(s, C, off, 10) for s, C, off in LARGE]
+# (shape, C, view offset, z-rows per chunk): every shape above has Z <= 96, so its chunks are DF_ROWS = 8 whole z-rows.  These reach the other
+# values of clamp(DF_CHUNK / Z, 1, DF_ROWS): 3 rows of 300 voxels (20 rows in all: the last chunk holds 2, and a chunk's voxel loop takes
+# four trips of the 256 threads), one row per chunk (Z = 600), and a row longer than DF_CHUNK (Z = 1100: the quotient 0 is clamped to 1).
+# X and Y stay at 3 to 5, where a randomness of 10 would push every voxel outside the volume: 1.5 leaves about half of them inside.
+CHUNKS = [((5, 4, 300), 1, 0, 3), ((5, 4, 300), 4, 0, 3), ((3, 5, 600), 1, 0, 1), ((4, 3, 1100), 1, 0, 1)]
+CASES = ([(s, C, off, r) for s, C, off in SMALL for r in (1.5, 10)] + [(s, C, off, 10) for s, C, off in LARGE] +
+         [(s, C, off, 1.5) for s, C, off, _ in CHUNKS])
 _REF = {}
+
+
+def _chunk_rows(Z):
+    """z-rows per chunk, as df_launch computes them from the constants of csrc/deform.hip."""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vnet_tensorflow_amd", "csrc", "deform.hip")).read()
+    rows, chunk = (int(re.search(r"\b%s\s*=\s*(\d+)" % n, src).group(1)) for n in ("DF_ROWS", "DF_CHUNK"))
+    return max(1, min(rows, chunk // Z)), chunk
+
+
+def test_chunk_shapes_reach_every_row_count():
+    """The shapes of CHUNKS are what their comment says under the kernel's present constants (a change of DF_ROWS / DF_CHUNK shows up here,
+    not as a case that silently tests the 8-row path again)."""
+    got = set()
+    for (X, Y, Z), _, _, want in CHUNKS:
+        rows, chunk = _chunk_rows(Z)
+        assert rows == want, ((X, Y, Z), rows, want)
+        got.add((rows, (X * Y) % rows != 0, rows * Z > 256, Z > chunk))
+    assert (3, True, True, False) in got and (1, False, True, False) in got and (1, False, True, True) in got
+    assert all(_chunk_rows(s[2])[0] == 8 for s, _, _ in SMALL + LARGE)
 
 
 def _inputs(shape, C, randomness):

@@ -236,9 +236,12 @@ def test_bn_chain(dev, kind, C, act):
     """The decoder's batch-norm chains evaluated in closed form as ONE normalisation of x (ops.bn_chain) against the
     oracle's layer-by-layer graph: kind 0 = act(BN3(BN1(x) + BN2(BN1(x)))), kind 1 = act(BNb(x + BNa(x)));
     gammas of both signs and small magnitude, a per-channel variance spread over 3 decades (so var is not >> eps)."""
+    _bn_chain_case(dev, kind, C, act, (2, 5, 6, 7))
+
+
+def _bn_chain_case(dev, kind, C, act, shp):
     from vnet_tensorflow_amd import ops
     rng = np.random.default_rng(100 * kind + C)
-    shp = (2, 5, 6, 7)
     scale = np.exp(rng.uniform(np.log(0.02), np.log(20.0), C))
     x = rng.standard_normal(shp + (C,)) * scale * (1.0 + rng.standard_normal(C) * 0.5)     # |mean| stays ~std: fp32 BN is conditioned by |mean|/std
     x = x.astype(np.float32).astype(np.float64)
