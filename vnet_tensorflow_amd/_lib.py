@@ -1,5 +1,5 @@
 """ctypes binding of libvnet_hip.so (include/vnet_hip.h, include/vnet_hip_unet.h, include/vnet_hip_head.h,
-include/vnet_hip_resample.h, include/vnet_hip_components.h, include/vnet_hip_deform.h).
+include/vnet_hip_resample.h, include/vnet_hip_components.h, include/vnet_hip_deform.h, include/vnet_hip_sample.h).
 
 The library is the product: there is NO fallback.  If the shared object is missing, or a
 kernel reports an error, this module raises -- nothing silently routes to PyTorch or the CPU.
@@ -163,6 +163,14 @@ SIGNATURES_DEFORM = {
     "vnet_bspline_deform_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _d, _d, _d, _vp]),
 }
 
+# seventh public header, include/vnet_hip_sample.h (the training pipeline's random tail on device-resident cases), same library
+SIGNATURES_SAMPLE = {
+    "vnet_cc_table_ws_bytes": (_sz, [_i, _i, _i]),
+    "vnet_cc_table": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "vnet_window_count": (_i, [_vp, _vp] + [_i] * 11 + [_vp]),
+    "vnet_sample_patch": (_i, [_vp, _vp, _vp, _vp] + [_i] * 11 + [_f, _u64, _vp]),
+}
+
 
 class WgradJob(ctypes.Structure):
     """include/vnet_hip.h: vnet_wgrad_job (one layer of vnet_conv_wgrad_b16_group)."""
@@ -221,10 +229,10 @@ def lib():
             elif name.endswith("_ws_bytes") or name.endswith("_stats_rows") or name == "vnet_conv_stats_from_reduce" or name == "vnet_packed_weight_floats":
                 setattr(L, name, _memo(fn))    # pure size queries, asked before every launch: answer repeats from a dict
         for name, (res, args) in list(SIGNATURES_UNET.items()) + list(SIGNATURES_HEAD.items()) + list(SIGNATURES_RESAMPLE.items()) + \
-                list(SIGNATURES_COMPONENTS.items()) + list(SIGNATURES_DEFORM.items()):
+                list(SIGNATURES_COMPONENTS.items()) + list(SIGNATURES_DEFORM.items()) + list(SIGNATURES_SAMPLE.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
-            if name in ("vnet_bn_head_ok", "vnet_bn_head_stats_rows", "vnet_bn_head_ws_bytes", "vnet_cc_ws_bytes"):
+            if name in ("vnet_bn_head_ok", "vnet_bn_head_stats_rows", "vnet_bn_head_ws_bytes", "vnet_cc_ws_bytes", "vnet_cc_table_ws_bytes"):
                 setattr(L, name, _memo(fn))
         _lib = L
     return _lib

@@ -123,7 +123,8 @@ class VolumeDataset(object):
     collective) is not sharded: every rank iterates all cases."""
 
     def __init__(self, data_dir, image_filenames, label_filename, classes, patch_shape, batch_size,
-                 train=True, seed=0, synthetic=None, rank=0, world=1, cache=None, transforms=None):
+                 train=True, seed=0, synthetic=None, rank=0, world=1, cache=None, transforms=None,
+                 device_tail=None, device_cache_bytes=16 << 30, max_components=4096):
         self.image_filenames, self.label_filename = list(image_filenames), label_filename
         self.classes, self.patch, self.batch = list(classes), tuple(patch_shape), int(batch_size)
         self.train, self.seed, self.epoch = train, int(seed), 0
@@ -148,6 +149,29 @@ class VolumeDataset(object):
                 raise FileNotFoundError("data directory %s does not exist" % data_dir)
             self.cases = sorted(os.path.join(data_dir, d) for d in os.listdir(data_dir)
                                 if os.path.isdir(os.path.join(data_dir, d)))
+        # device_tail (a torch device; TrainingSetting.SampleOnDevice): prepared cases -- the case after the pipeline's deterministic
+        # prefix -- live in device memory under an LRU byte budget, the random tail's index decisions stay on the host and one kernel
+        # writes each sample into a device batch (vnet_tensorflow_amd/sample.py).  Only the tails
+        # transforms.plan_tail recognises; any other keeps the loader path below
+        self.device_tail, self._tail = None, None
+        if device_tail is not None:
+            from .transforms import deterministic_prefix, plan_tail
+            self._tail_at = deterministic_prefix(transforms) if transforms is not None else 0
+            self._tail = plan_tail(transforms[self._tail_at:]) if transforms is not None else None
+            if self._tail is None:
+                print("VolumeDataset: the pipeline's random tail is not one the device serves (ConfidenceCrop2 | RandomCrop, then "
+                      "RandomFlip, then RandomNoise); samples keep the loader path")
+            elif tuple(self._tail.crop.output_size) != self.patch:
+                raise ValueError("the pipeline's crop produces %s samples, PatchShape is %s" % (tuple(self._tail.crop.output_size), self.patch))
+            else:
+                import collections
+                import torch
+                self.device_tail = torch.device(device_tail)
+                self.device_cache_bytes, self.max_components = int(device_cache_bytes), int(max_components)
+                # case -> (image, label, (n, rows) | None) on the device, least recently used first.  No lock of its own: it is
+                # touched only inside ops.side_work, whose lock is exclusive (one loader thread at a time, and never during a capture)
+                self._dev_cache, self._dev_bytes, self._dev_host_only = collections.OrderedDict(), 0, set()
+                self.device_stats = {"uploads": 0, "evictions": 0, "host_samples": 0}
         if self.train and self.steps_per_epoch() == 0:
             raise ValueError("%d cases give no full batch for %d rank(s) x batch %d: every rank needs at least one batch per "
                              "epoch (a rank without work would sit in no collective at all)" % (len(self.cases), world, self.batch))
@@ -215,9 +239,91 @@ class VolumeDataset(object):
         """(image shape, label shape) of one batch: [B, *patch, Cin] float32 and [B, *patch, 1] int32."""
         return (self.batch,) + tuple(self.patch) + (len(self.image_filenames),), (self.batch,) + tuple(self.patch) + (1,)
 
+    def _prepared_split(self, case):
+        """The case after the deterministic prefix, whether or not the host cache is on (the device cache is what keeps it)."""
+        from .transforms import run_pipeline
+        if self.cache is not None:
+            return self._prepared(case)[0]           # (kept on the host as well: a re-upload after an eviction prepares nothing again)
+        image, label = self._load(case, keep=False)
+        return run_pipeline(self.transforms[:self._tail_at], {'image': image, 'label': label, 'spacing': self._spacing(case)}, None)
+
+    def _device_case(self, case):
+        """(image float32 [X,Y,Z,C], label int32 [X,Y,Z], component table | None) on the device, or None when the case takes the NumPy
+        path: larger than the budget, or more components than max_components.  Called inside ops.side_work.  The table belongs to the
+        prepared case -- a pure function of the file and the deterministic prefix -- so it is computed once, at the upload, and leaves
+        the cache with the case."""
+        import torch
+        from . import ops
+        from .transforms import ConfidenceCrop2
+        if case in self._dev_host_only:
+            return None
+        entry = self._dev_cache.get(case)
+        if entry is not None:
+            self._dev_cache.move_to_end(case)
+            return entry
+        sample = self._prepared_split(case)
+        image = np.ascontiguousarray(sample['image'], dtype=np.float32)
+        label = np.ascontiguousarray(sample['label'], dtype=np.int32)
+        nbytes = image.nbytes + label.nbytes
+        if nbytes > self.device_cache_bytes:
+            self._dev_host_only.add(case)
+            return None
+        while self._dev_cache and self._dev_bytes + nbytes > self.device_cache_bytes:
+            _, old = self._dev_cache.popitem(last=False)
+            self._dev_bytes -= old[0].numel() * 4 + old[1].numel() * 4
+            self.device_stats["evictions"] += 1
+        di, dl = torch.from_numpy(image).to(self.device_tail), torch.from_numpy(label).to(self.device_tail)
+        table = None
+        if isinstance(self._tail.crop, ConfidenceCrop2):
+            need = ops._lib.lib().vnet_cc_table_ws_bytes(*label.shape)
+            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device_tail)     # (this thread's, on its side stream)
+            table = ops.component_table(dl, self.max_components, ws=ws)
+            if table[0] > self.max_components:
+                self._dev_host_only.add(case)
+                return None
+        entry = (di, dl, table)
+        self._dev_cache[case] = entry
+        self._dev_bytes += nbytes
+        self.device_stats["uploads"] += 1
+        return entry
+
+    def _make_batch_device(self, cases, seeds):
+        """Device tensors (image float32 [B,*P,Cin], label int32 [B,*P,1]); wholly inside ops.side_work: the loader thread's
+        uploads, launches and read-backs run on its own stream and never while the step graph is being captured."""
+        import torch
+        from . import ops
+        from .transforms import run_pipeline
+        si, sl = (len(cases),) + self.batch_shapes()[0][1:], (len(cases),) + self.batch_shapes()[1][1:]
+        with ops.side_work(self.device_tail):
+            img = torch.empty(si, dtype=torch.float32, device=self.device_tail)
+            lab = torch.empty(sl, dtype=torch.int32, device=self.device_tail)
+            for i, (case, sd) in enumerate(zip(cases, seeds)):
+                rng = np.random.default_rng(sd)
+                entry = self._device_case(case)
+                if entry is None:
+                    self.device_stats["host_samples"] += 1
+                    sample = run_pipeline(self.transforms[self._tail_at:], self._prepared_split(case), rng)
+                    if tuple(sample['label'].shape) != self.patch:
+                        raise ValueError("the transform pipeline produced a %s sample, PatchShape is %s" % (tuple(sample['label'].shape), self.patch))
+                    img[i].copy_(torch.from_numpy(np.ascontiguousarray(sample['image'], dtype=np.float32)))
+                    lab[i, ..., 0].copy_(torch.from_numpy(np.ascontiguousarray(sample['label'], dtype=np.int32)))
+                    continue
+                di, dl, table = entry
+                shape = tuple(dl.shape)
+                if any(s < p for s, p in zip(shape, self.patch)):
+                    raise ValueError("the prepared case is %s, smaller than PatchShape %s (put a Padding in front of the crop, like "
+                                     "the reference's pipeline3D.yaml)" % (shape, self.patch))
+                start, mask, sigma, seed = self._tail.draw(shape, rng, lambda: table,
+                                                           lambda s, n, lo, hi: ops.window_count(dl, s, n, lo, hi))
+                ops.sample_patch(di, dl, start, self.patch, mask, sigma, seed, img[i], lab[i])
+        return img, lab
+
     def make_batch(self, cases, seeds, out=None):
         """out = (image float32 [B,*P,Cin], label int32 [B,*P,1]) NumPy arrays to fill (e.g. views of pinned host tensors: the
-        crop is then the ONLY copy between the cached volume and the DMA source); None: new arrays."""
+        crop is then the ONLY copy between the cached volume and the DMA source); None: new arrays.
+        With device_tail the batch is made on the device and returned as device tensors (`out` is not used)."""
+        if self.device_tail is not None:
+            return self._make_batch_device(cases, seeds)
         imgs, labs = [], []
         for i, (case, sd) in enumerate(zip(cases, seeds)):
             if self.transforms is not None:
@@ -257,6 +363,9 @@ class Prefetcher(object):
 
     def _job(self, cases, seeds):
         import torch
+        if getattr(self.dataset, "device_tail", None) is not None:
+            # the batch is made in device memory (VolumeDataset._make_batch_device): nothing to pin, no pinned allocation
+            return self.dataset.make_batch(cases, seeds)
         if self.pin and torch.cuda.is_available() and len(cases) == self.dataset.batch and hasattr(self.dataset, "batch_shapes"):
             # crop straight into pinned memory (torch's caching host allocator hands a block out again only after the
             # asynchronous copies that read it have finished): one host copy per batch instead of three

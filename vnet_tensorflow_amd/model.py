@@ -149,6 +149,7 @@ class _DeviceFeeder(object):
         if not self.cuda:
             self.slots[k] = (img.to(self.device), lab.to(self.device))
             return
+        resident = img.is_cuda and lab.is_cuda       # (TrainingSetting.SampleOnDevice: the loader made the batch in device memory)
         with torch.cuda.stream(self.copy_stream):
             if self.done[k] is not None:
                 self.copy_stream.wait_event(self.done[k])          # the step that read this slot has finished
@@ -157,8 +158,18 @@ class _DeviceFeeder(object):
                 di, dl = old
                 di.copy_(img, non_blocking=True)
                 dl.copy_(lab, non_blocking=True)
+            elif resident:
+                # (.to() of a device tensor is the tensor itself: the slot must be this stream's own block)
+                di, dl = torch.empty_like(img), torch.empty_like(lab)
+                di.copy_(img, non_blocking=True)
+                dl.copy_(lab, non_blocking=True)
             else:
                 di, dl = img.to(self.device, non_blocking=True), lab.to(self.device, non_blocking=True)
+            if resident:
+                # the source blocks belong to a loader thread's stream (finished: ops.side_work synchronises before it returns);
+                # without this the allocator could hand them back to that stream while the copy above is still in flight
+                img.record_stream(self.copy_stream)
+                lab.record_stream(self.copy_stream)
             self.slots[k] = (di, dl)
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
@@ -303,6 +314,10 @@ class image2label(object):
         self.loss_alpha = T['Loss'].get('Alpha', 1)
         self.training_pipeline = T.get('Pipeline')
         self.deform_on_device = bool(T.get('DeformOnDevice', False))
+        # extension (opt-in): the train pipeline's random tail -- crop, flip, noise -- on prepared cases kept in device memory
+        # (data.VolumeDataset(device_tail=...)); DeviceCacheGB: the byte budget of those cases
+        self.sample_on_device = bool(T.get('SampleOnDevice', False))
+        self.device_cache_gb = float(T.get('DeviceCacheGB', 16))
         E = self.config.get('EvaluationSetting', {})
         self.checkpoint_path = E.get('CheckpointPath')
         ED = E.get('Data', {})
@@ -817,9 +832,13 @@ class image2label(object):
             on_dev = bool(getattr(self, "deform_on_device", False)) and self.device.type == "cuda"
             tf = vtf.build_pipeline(self.training_pipeline, "train" if train else "test", geometry=True, deformation=True,
                                     device=self.device if on_dev else None)
+        tail = {}
+        if train and tf is not None and bool(getattr(self, "sample_on_device", False)) and self.device.type == "cuda":
+            # the training set only: the test pass keeps the NumPy path
+            tail = {"device_tail": self.device, "device_cache_bytes": int(float(getattr(self, "device_cache_gb", 16)) * 2 ** 30)}
         return vdata.VolumeDataset(data_dir, self.image_filenames, self.label_filename, self.label_classes,
                                    self.patch_shape, self.batch_size, train=train, synthetic=self.synthetic,
-                                   rank=self.rank, world=self.world, transforms=tf)
+                                   rank=self.rank, world=self.world, transforms=tf, **tail)
 
     # -- reference model.py:632-815 ---------------------------------------------------------------------------
     @in_context

@@ -1792,6 +1792,99 @@ def volume_threshold(label, volume, spacing=(1.0, 1.0, 1.0)):
     return out if out is not None else _cc_host(label, _model.volume_threshold, volume, spacing)
 
 
+# ---- the training pipeline's random tail on device-resident cases (include/vnet_hip_sample.h; rules: vnet_tensorflow_amd/sample.py) ----
+# These run on loader threads inside side_work: they launch on torch's current stream of the CALLING thread, never on the redirect of
+# the parameter-gradient section (_LAUNCH_ON is process-wide and belongs to the training step).
+CC_ROW = 8                 # VNET_CC_ROW: representative, count, lo[3], hi[3]
+
+
+def _thread_stream(device):
+    return torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch._C._cuda_getDevice())
+
+
+def _sample_label(label, what):
+    if label.dim() != 3 or label.numel() == 0:
+        raise VnetHipError("%s: takes a non-empty [X,Y,Z] label map, got %s" % (what, tuple(label.shape)))
+    _need_gpu(label, what, any_dtype=True)
+    if label.dtype != torch.int32 or not label.is_contiguous():
+        raise VnetHipError("%s: the label map is a contiguous int32 tensor, got %s" % (what, label.dtype))
+    return tuple(int(v) for v in label.shape)
+
+
+def _three(v, what):
+    v = tuple(int(x) for x in v)
+    if len(v) != 3:
+        raise ValueError("%s takes three values" % what)
+    return v
+
+
+def component_table(label, max_components=4096, ws=None):
+    """The face-connected components of label != 0 (int32 [X,Y,Z] on the device) as a table: (n, int32 NumPy array
+    [min(n, max_components), 8]), row k = {representative, voxel count, lo_x, lo_y, lo_z, hi_x, hi_y, hi_z} (hi inclusive) of
+    scipy.ndimage.label's component k + 1; n is the true number of components also when it exceeds max_components.  One read-back.
+    ws: a uint8 device tensor of at least vnet_cc_table_ws_bytes; None = ops.workspace (the training loop's thread only: a loader
+    thread passes its own)."""
+    X, Y, Z = _sample_label(label, "component_table")
+    cap = int(max_components)
+    if cap < 1:
+        raise ValueError("component_table: max_components %d" % cap)
+    L = _lib.lib()
+    need = L.vnet_cc_table_ws_bytes(X, Y, Z)
+    if need == 0:
+        raise VnetHipError("component_table: %dx%dx%d has more voxels than an int32 indexes" % (X, Y, Z))
+    if ws is None:
+        ws = workspace(need, label.device)
+    elif ws.numel() * ws.element_size() < need:
+        raise VnetHipError("component_table: ws holds %d bytes, %d needed" % (ws.numel() * ws.element_size(), need))
+    out = torch.empty(cap * CC_ROW + 1, dtype=torch.int32, device=label.device)       # the rows, then n: one copy brings both
+    with _Timed("cc table %dx%dx%d" % (X, Y, Z), 0.0, 4.0 * label.numel() * 7):
+        check(L.vnet_cc_table(_ptr(label), out.data_ptr() + 4 * cap * CC_ROW, _ptr(out), cap, X, Y, Z, _ptr(ws), need,
+                              _thread_stream(label.device)), "vnet_cc_table")
+    host = out.cpu().numpy()
+    n = int(host[-1])
+    return n, host[:min(n, cap) * CC_ROW].reshape(-1, CC_ROW).copy()
+
+
+def window_count(label, start, size, lo, hi):
+    """(number of voxels with lo <= label <= hi, sum of the labels) over the window start .. start + size of an int32 [X,Y,Z] device
+    label map, as Python ints.  One read-back."""
+    X, Y, Z = _sample_label(label, "window_count")
+    start, size = _three(start, "window_count: start"), _three(size, "window_count: size")
+    out = torch.empty(2, dtype=torch.int64, device=label.device)
+    check(_lib.lib().vnet_window_count(_ptr(label), _ptr(out), X, Y, Z, *start, *size, int(lo), int(hi), _thread_stream(label.device)),
+          "vnet_window_count")
+    c, s = out.tolist()
+    return int(c), int(s)
+
+
+def sample_patch(image, label, start, patch, flip, sigma, seed, out_image, out_label):
+    """One sample of a batch, written in place: out_image (float32 [P0,P1,P2,C]) and out_label (int32 [P0,P1,P2] or [P0,P1,P2,1]) get
+    the window of `patch` voxels at `start` of image (float32 [X,Y,Z,C]) and label (int32 [X,Y,Z]), axis a reversed within the patch
+    where bit a of `flip` is set, plus sigma * N(0, 1) on the image, the deviates a function of (seed, output element) alone
+    (vnet_tensorflow_amd/sample.py).  sigma 0: the crop bit for bit.  The outputs are the caller's slots: dense, any 4-byte offset (an
+    image slot off a 16-byte boundary takes the one-channel path, with the same values)."""
+    X, Y, Z = _sample_label(label, "sample_patch")
+    start, patch = _three(start, "sample_patch: start"), _three(patch, "sample_patch: patch")
+    if image.dim() != 4 or tuple(image.shape[:3]) != (X, Y, Z):
+        raise VnetHipError("sample_patch: image %s does not go with label %s" % (tuple(image.shape), (X, Y, Z)))
+    C = int(image.shape[3])
+    for t in (image, out_image):
+        _need_gpu(t, "sample_patch")
+    _need_gpu(out_label, "sample_patch", any_dtype=True)
+    if out_label.dtype != torch.int32:
+        raise VnetHipError("sample_patch: out_label is int32, got %s" % (out_label.dtype,))
+    if tuple(out_image.shape) != patch + (C,) or tuple(out_label.shape) not in (patch, patch + (1,)):
+        raise VnetHipError("sample_patch: outputs %s / %s for a patch %s of %d channel(s)" % (tuple(out_image.shape), tuple(out_label.shape), patch, C))
+    if not (image.is_contiguous() and out_image.is_contiguous() and out_label.is_contiguous()):
+        raise VnetHipError("sample_patch: image and both slots are dense")
+    if any(s < 0 or s + p > n for s, p, n in zip(start, patch, (X, Y, Z))):
+        raise ValueError("sample_patch: window %s + %s leaves the volume %s" % (start, patch, (X, Y, Z)))
+    with _Timed("sample patch %dx%dx%d %d" % (patch + (C,)), 0.0, 8.0 * out_image.numel() + 8.0 * out_label.numel()):
+        check(_lib.lib().vnet_sample_patch(_ptr(image), _ptr(label), _ptr(out_image), _ptr(out_label), X, Y, Z, C, *start, *patch,
+                                           int(flip), float(sigma), int(seed) & (2 ** 64 - 1), _thread_stream(image.device)),
+              "vnet_sample_patch")
+
+
 # ---- stand-alone activation (API parity with layers2.prelu; the networks use the fused bn_act) ------------
 class _ActFn(torch.autograd.Function):
     @staticmethod

@@ -163,6 +163,17 @@ class RandomCrop(object):
                 break
         return {'image': np.ascontiguousarray(image[sl]), 'label': np.ascontiguousarray(label[sl])}
 
+    def start_index(self, shape, rng, table, count):
+        """The start index of the window __call__ would cut from a label map of `shape`, drawing from `rng` exactly as __call__ does
+        (the short-circuited rng.random() included), without the voxels: count(start, size, lo, hi) -> (number of voxels of the window
+        with lo <= label <= hi, sum of its labels).  `table` is not asked (ConfidenceCrop2.start_index reads it)."""
+        old, new = tuple(shape), self.output_size
+        size = tuple(min(o, n) for o, n in zip(old, new))
+        while True:
+            start = [0 if o <= n else int(rng.integers(0, o - n)) for o, n in zip(old, new)]
+            if int(count(start, size, 1, 255)[0]) >= self.min_pixel or rng.random() <= self.drop_ratio:
+                return start
+
 
 class RandomNoise(object):
     """sitk.AdditiveGaussianNoiseImageFilter(mean 0, standard deviation sigma) on every channel."""
@@ -243,6 +254,37 @@ class ConfidenceCrop2(object):
             index.append(ix)
         image, label = self._crop(image, label, index)
         return {'image': image, 'label': label}
+
+    def start_index(self, shape, rng, table, count):
+        """The start index of the window __call__ would cut from a label map of `shape`, drawing from `rng` exactly as __call__ does
+        (the RandomEmptyRegion loop included), without the voxels: table() -> (n, rows) with row k = {representative, count, lo[3],
+        hi[3] inclusive} of ndimage.label's component k + 1 (asked only on the branch that labels), count(start, size, lo, hi) ->
+        (number of voxels of the window with lo <= label <= hi, sum of its labels)."""
+        shape = tuple(shape)
+        choices = [0] * int(10 * (1 - self.probability)) + [1] * int(10 * self.probability)
+        label_type = choices[int(rng.integers(len(choices)))]
+
+        def pick_random():
+            while True:
+                index = self._random_index(shape, rng)
+                if not self.random_empty_region or count(index, self.output_size, 1, 255)[1] < 1:
+                    return index
+        if label_type == 0:
+            return pick_random()
+        n, rows = table()
+        if n == 0:
+            return pick_random()
+        row = rows[int(rng.integers(n))]
+        index = []
+        for i in range(3):
+            lo, ext = int(row[2 + i]), int(row[5 + i]) + 1 - int(row[2 + i])
+            ix = lo + int(ext / 2) - int(self.output_size[i] / 2) + int(rng.integers(-self.rand_range[i], self.rand_range[i] + 1))
+            if shape[i] - ix - 1 < self.output_size[i]:
+                ix = shape[i] - self.output_size[i] - 1
+            if ix < 0:
+                ix = 0
+            index.append(ix)
+        return index
 
 
 class Resample(object):
@@ -364,6 +406,41 @@ def deterministic_prefix(transforms):
     while n < len(transforms) and not isinstance(transforms[n], _RANDOM):
         n += 1
     return n
+
+
+class TailPlan(object):
+    """What plan_tail recognised: the crop (ConfidenceCrop2 | RandomCrop), then RandomFlip or None, then RandomNoise or None."""
+
+    def __init__(self, crop, flip, noise):
+        self.crop, self.flip, self.noise = crop, flip, noise
+
+    def draw(self, shape, rng, table, count):
+        """(start index, flip mask, sigma, noise seed) of one sample, drawn from `rng` in the order the transforms would: the crop's
+        draws (start_index), RandomFlip's coin, and for RandomNoise ONE 64-bit seed (the NumPy transform draws the deviates
+        themselves, so the noise of the two paths differs; everything in front of it does not)."""
+        start = self.crop.start_index(shape, rng, table, count)
+        mask = 0
+        if self.flip is not None and int(rng.integers(2)):
+            mask = sum(1 << i for i, f in enumerate(self.flip.axes) if f)
+        sigma, seed = 0.0, 0
+        if self.noise is not None:
+            sigma, seed = float(self.noise.sigma), int(rng.integers(0, 2 ** 64, dtype=np.uint64))
+        return start, mask, sigma, seed
+
+
+def plan_tail(transforms):
+    """TailPlan of a random tail that a device-resident case can serve -- one of ConfidenceCrop2 | RandomCrop, then optionally
+    RandomFlip, then optionally RandomNoise, in that order and nothing else -- or None (any other tail, a BSplineDeformation in front
+    of the crop included: the dataset then keeps the loader path)."""
+    tf = list(transforms)
+    if not tf or type(tf[0]) not in (ConfidenceCrop2, RandomCrop):
+        return None
+    crop, rest = tf[0], tf[1:]
+    flip = rest.pop(0) if rest and type(rest[0]) is RandomFlip else None
+    noise = rest.pop(0) if rest and type(rest[0]) is RandomNoise else None
+    if rest:
+        return None
+    return TailPlan(crop, flip, noise)
 
 
 def run_pipeline(transforms, sample, rng):
