@@ -31,7 +31,10 @@ axes): every (variant, axis, class) triple occurs, plus one case per variant wit
 (Full pairwise covering of 5 x 5 x 5 classes needs 25 cases per variant, about 1300 cases: measured, the 353 cases cost 20 % of the rest
 of the GPU suite, four times as many would cost most of it.  pair_coverage() counts the class pairs that are covered.)  Extents start at the smallest k and grow, class preserved, until the variant's `accept` holds (e.g. >= 256 bricks
 for the persistent 16-cout kernel).  `extra` rows of a variant are hand-picked shapes for the conditions no class realises: fewer /
-more items than workgroups, split 1 / > 1, W = 7 / 8 / 9."""
+more items than workgroups, split 1 / > 1, W = 7 / 8 / 9.
+
+OPERAND PROFILES (PROFILES, operands_x3, x3_runs; further down): the f32x3 rows run a second time on operands with 9-10 and 18
+significant bits, which fill the m and l pieces of the split -- exactness argument, limit and sizing are stated there."""
 import collections
 import functools
 import zlib
@@ -757,6 +760,298 @@ def bound(c, d):
 def stored(c, a):
     """What the device stores for the exact result a: the value itself (fp32 tensors), round_bf16 of it (bf16 tensors)."""
     return O.round_bf16(a) if c.v.mode == "bf16" else a
+
+
+# ---- operand profiles of the f32x3 rows: operands that fill the m and l pieces ---------------------------------------------------
+# The f32x3 kernels (csrc/conv_x3.h) split an fp32 operand exactly into three bf16 pieces h = RNE(x), m = RNE(x - h), l = RNE(x - h - m)
+# and form a product from the six streams hh, hm, mh, mm, hl, lh.  Integer operands are bf16-exact: m = l = 0, five streams multiply
+# zeros.  The profiles below draw operands with 9+ (depth 2) and 18 (depth 3) significant bits and keep the comparison EXACT:
+#
+#   every operand is k * 2^-q with an integer k (q = 0 / Q2 / Q3 for depth 1 / 2 / 3), so every product of every stream is a whole
+#   multiple of the launch's unit 2^-(qa + qb), and every fp32 partial sum of every summation order is exact when
+#     (E1) the three dropped terms ml, lm, ll are identically zero (one side of a launch has no m or the other no l, and no l meets an l);
+#     (E2) sum |a| |b| / unit < 2^24 for every output element (bound_x3: the oracle on magnitudes, per output in its own unit).
+#   WHY 2^24 AND NOT THE INTEGER SWEEP'S 2^20: a depth-3 value of magnitude ~1 is at least 2^17 units, so 2^20 would leave 8 terms per
+#   output, and a filter in which every (tap, input channel) is used has at least 125 Cin / Cout terms per output.  The 4 bits of margin
+#   are not needed: v_mfma_f32_16x16x32_bf16 aligns the 32 products and the accumulator of an instruction to the largest term and keeps
+#   at least 26 bits from that term's leading bit down -- profiles/r06_mfma_round_probe.txt: "c=0: 2^24 - 2^24 + 30 x 1.0" gives exactly
+#   30 and "c=2^24, p0 = -2^24, + 2 x 1.0" exactly 2 (the unit survives 24 bits below the largest term; wrong only from 2^28), and
+#   "c=1 + 32 x 0.25 ulp" gives exactly +8 ulp (terms of 2^-25 of the largest are added exactly).  With every term and the accumulator
+#   below 2^24 units the unit is at most 23 bits below the largest term's leading bit: two bits inside that window.  Everything
+#   outside the instruction -- sign flips, the four-wave and split-K reductions, the bias -- is plain fp32 on multiples of the unit
+#   below 2^24 units: exact.
+#
+# A depth-3 operand is a mix: a share of 18-bit values k in [2^17, 2^18) chosen so that l != 0 ("L" elements, 2^17.6 units each), the
+# rest 9-10-bit values k in [2^8, 2^10) with m != 0 (2^9.2 units): m != 0 everywhere, l != 0 in the L share.  The share is what (E2)
+# pays for: an output that sums n terms against magnitude-1 partners holds n * share * 2^17.6 units, so share <= 2^24 / (n 2^17.6) / 1.6
+# (the largest of many random sums lies about 1.6 x above the mean).  n is at least 125 * max(Cin, Cout) / Cout for the forward launch of a
+# filter that uses every (tap, input channel) and every (tap, output channel): 34 % at n = 125, 17 % at 250, 4 % at 1000 (128 -> 16).
+# L_FLOOR states that per case; a case over the limit gets sparser operands (the thinning factor), never a wider limit.
+X3_LIMIT = float(1 << 24)
+Q2, Q3 = 8, 17
+PROFILES = ("x-deep", "w-deep", "dy-deep", "mid-dense-x", "mid-dense-w", "mid-mid")
+# depth of (x, w, dy) per profile
+DEPTHS = {"x-deep": (3, 1, 1), "w-deep": (1, 3, 1), "dy-deep": (1, 1, 3), "mid-dense-x": (2, 1, 1), "mid-dense-w": (1, 2, 1), "mid-mid": (2, 2, 2)}
+DEEP = {"x-deep": "x", "w-deep": "w", "dy-deep": "dy", "mid-dense-x": "x", "mid-dense-w": "w"}          # the dense deep operand
+QOF = {1: 0, 2: Q2, 3: Q3}
+M_FLOOR = 0.90                             # share of the deep operand's elements with m != 0 (the draws give 100 %)
+MEAN_L, MEAN_M = 1.5 * 2.0 ** 17, 1.5 * 2.0 ** 9     # mean |k| of an L element, of a two-piece element
+
+
+def x3_cases():
+    return tuple(c for c in generate() if c.v.mode == "x3")
+
+
+def x3_runs():
+    """[(case, profile)] that the tests run: every f32x3 case under the three deep profiles; the mid-dense and mid-mid profiles on one
+    case per row, the one with the most ragged axes (all three, except on the narrow rows, whose x extent is always 8) -- measured,
+    all 51 cases under all six profiles cost 57 % of the rest of the GPU suite, and the rule is a quarter."""
+    cs = x3_cases()
+    ragged = {}
+    for c in cs:
+        n = sum(k in RAGGED for k in case_classes(c))
+        if c.variant not in ragged or n > ragged[c.variant][0]:
+            ragged[c.variant] = (n, c)
+    keep = set(c for _, c in ragged.values())
+    return tuple((c, p) for c in cs for p in PROFILES if p in ("x-deep", "w-deep", "dy-deep") or c in keep)
+
+
+def split3_np(a):
+    """(h, m, l) of the f32x3 split, restated: three successive round-to-nearest-even bf16 roundings (float64 arrays)."""
+    h = O.round_bf16(a)
+    m = O.round_bf16(a - h)
+    return h, m, O.round_bf16(a - h - m)
+
+
+def _signs(rng, shape):
+    return rng.integers(0, 2, shape) * 2.0 - 1.0
+
+
+def _two_piece(rng, shape, hi=10):
+    """k in [2^8, 2^hi) with m != 0, random sign (units of the caller's 2^-q)."""
+    k = rng.integers(1 << 8, 1 << hi, shape).astype(np.float64)
+    for _ in range(64):
+        bad = split3_np(k)[1] == 0
+        if not bad.any():
+            break
+        k[bad] = rng.integers(1 << 8, 1 << hi, int(bad.sum()))
+    return k * _signs(rng, shape)
+
+
+def _three_piece(rng, shape):
+    """k in [2^17, 2^18) with l != 0, random sign."""
+    k = rng.integers(1 << 17, 1 << 18, shape).astype(np.float64)
+    for _ in range(256):
+        bad = split3_np(k)[2] == 0
+        if not bad.any():
+            break
+        k[bad] = rng.integers(1 << 17, 1 << 18, int(bad.sum()))
+    return k * _signs(rng, shape)
+
+
+def _deep3(rng, shape, share):
+    """Depth 3, dense: L elements with probability `share`, two-piece elements elsewhere; in units of 2^-Q3."""
+    k = _two_piece(rng, shape)
+    mask = rng.random(shape) < share
+    k[mask] = _three_piece(rng, int(mask.sum()))
+    return k * 2.0 ** -Q3
+
+
+def _deep2(rng, shape, share=1.0, hi=10):
+    """Depth 2: two-piece elements with probability `share`, one-piece fill (|k| <= 3) elsewhere; in units of 2^-Q2."""
+    k = rng.integers(1, 4, shape).astype(np.float64) * _signs(rng, shape)
+    mask = rng.random(shape) < share
+    k[mask] = _two_piece(rng, int(mask.sum()), hi)
+    return k * 2.0 ** -Q2
+
+
+def _bricks_of(shape, brick):
+    B, D, H, W = shape[:4]
+    return B * cdiv(D, brick[0]) * cdiv(H, brick[1]) * cdiv(W, brick[2])
+
+
+def _sparse(rng, shape, density, brick, vals, per_channel=None):
+    """A sparse [B, D, H, W, C] tensor of the values vals(rng, n): one non-zero in every brick of the tiling (at a random voxel and
+    channel of the brick; per_channel caps how many of these a channel may carry -- bricks past the cap stay empty and are counted by
+    empty_bricks()), plus independent non-zeros with probability `density`."""
+    B, D, H, W, C = shape
+    mask = rng.random(shape) < density
+    nb = _bricks_of(shape, brick)
+    ncover = nb if per_channel is None else min(nb, max(1, int(per_channel)) * C)
+    ids = rng.permutation(nb)[:ncover]
+    nz, ny, nx = cdiv(D, brick[0]), cdiv(H, brick[1]), cdiv(W, brick[2])
+    bx, r = ids % nx, ids // nx
+    by, r = r % ny, r // ny
+    bz, b = r % nz, r // nz
+    lo = lambda i, t, e: i * t + (rng.random(len(ids)) * np.minimum(t, e - i * t)).astype(np.int64)
+    mask[b, lo(bz, brick[0], D), lo(by, brick[1], H), lo(bx, brick[2], W), np.arange(len(ids)) % C] = True
+    a = np.zeros(shape)
+    a[mask] = vals(rng, int(mask.sum()))
+    return a
+
+
+def _cover(rng, shape, n, brick, vals):
+    """A sparse tensor with about n non-zeros per channel (what (E2) lets one element of the filter gradient sum): 30 % of them go to
+    one voxel per brick, the rest anywhere; where the bricks outnumber that, their part grows to at most half -- density first -- and
+    only past that do bricks stay empty (the host test caps their share)."""
+    M, C = int(np.prod(shape[:4])), shape[4]
+    nb = _bricks_of(shape, brick)
+    if 0.3 * n * C >= nb:
+        return _sparse(rng, shape, min(1.0, 0.7 * n / M), brick, vals, 0.3 * n)
+    part = min(0.5, 1.05 * nb / (n * C))
+    return _sparse(rng, shape, min(1.0, (1.0 - part) * n / M), brick, vals, part * n)
+
+
+def empty_bricks(a, brick):
+    """Share of the tiling's bricks in which the [B, D, H, W, C] tensor a is zero everywhere."""
+    B, D, H, W, C = a.shape
+    nzv = np.abs(a).max(-1) > 0
+    pad = [(0, 0)] + [(0, rup(e, t) - e) for e, t in zip((D, H, W), brick)]
+    nzv = np.pad(nzv, pad).reshape(B, rup(D, brick[0]) // brick[0], brick[0], rup(H, brick[1]) // brick[1], brick[1], rup(W, brick[2]) // brick[2], brick[2])
+    return 1.0 - float(nzv.any(axis=(2, 4, 6)).mean())
+
+
+def _filter_cover(rng, Cin, O_, vals):
+    """A sparse [5, 5, 5, Cin, O] filter with the fewest non-zeros in which every (tap, input channel) has a weight for some output
+    channel and every (tap, output channel) one for some input channel: per tap, max(Cin, O) weights on a rotated diagonal."""
+    w = np.zeros((125, Cin, O_))
+    n = max(Cin, O_)
+    j = np.arange(n)
+    for t in range(125):
+        s = int(rng.integers(0, n))
+        w[t, j % Cin, (j + s) % O_] = vals(rng, n)
+    return w.reshape(5, 5, 5, Cin, O_)
+
+
+def _unit_ints(rng, n):
+    return _signs(rng, n)
+
+
+def l_floor(c, profile):
+    """The share of l != 0 elements the case's deep operand must reach: 20 %, or what (E2) leaves -- see the header of this section."""
+    Cin = c.C0 + c.C1
+    n = {"x-deep": 125 * max(Cin, c.O) // c.O, "dy-deep": 125 * max(Cin, c.O) // Cin}.get(profile)
+    if n is None:
+        return 0.20 if profile == "w-deep" else 0.0
+    return min(0.20, 0.5 * X3_LIMIT / (1.6 * n * MEAN_L))
+
+
+def _draw_x3(c, profile, thin):
+    """The operands of (case, profile) at thinning factor `thin` (1 = the design sizes; operands_x3 lowers it until (E2) holds)."""
+    rng = np.random.default_rng(zlib.crc32(("%s/%s" % (c.cid, profile)).encode()))
+    B, (D, H, W), Cin, Co = c.B, c.dims, c.C0 + c.C1, c.O
+    xs, ys, M = (B, D, H, W, Cin), (B, D, H, W, Co), B * D * H * W
+    brick = x3_brick(W)
+    budget = X3_LIMIT * thin / 1.6                       # the expected units of an output's sum of magnitudes
+    nfw, nbw = 125 * max(Cin, Co) // Co, 125 * max(Cin, Co) // Cin      # terms of a forward / backward-data output against the cover filter
+    share3 = lambda n: float(min(0.5, max(0.0, (budget / n - MEAN_M) / MEAN_L)))
+    ones = lambda sh: _signs(rng, sh)
+    if profile == "x-deep":
+        p = share3(nfw)
+        x = _deep3(rng, xs, p)
+        w = _filter_cover(rng, Cin, Co, _unit_ints)
+        ndy = budget / (p * MEAN_L + MEAN_M)              # non-zeros of a dy channel: the terms of a filter-gradient element
+        dy = _cover(rng, ys, ndy, brick, _unit_ints)
+    elif profile == "dy-deep":
+        p = share3(nbw)
+        dy = _deep3(rng, ys, p)
+        w = _filter_cover(rng, Cin, Co, _unit_ints)
+        nx_ = budget / (p * MEAN_L + MEAN_M)
+        x = _cover(rng, xs, nx_, brick, _unit_ints)
+    elif profile == "w-deep":
+        p = 0.3
+        w = _deep3(rng, (5, 5, 5, Cin, Co), p)
+        per = budget / (p * MEAN_L + MEAN_M)              # non-zero partners in an output's receptive field
+        x = _sparse(rng, xs, min(1.0, per / (125 * Cin)), brick, _unit_ints)
+        dy = _sparse(rng, ys, min(1.0, per / (125 * Co)), brick, _unit_ints)
+    elif profile == "mid-dense-x":                        # x two-piece everywhere; w and dy integers, dense where (E2) lets them
+        x = _deep2(rng, xs)
+        w = _sparse(rng, (1, 5, 5, 5, Cin * Co), min(1.0, budget * 1.4 / (125 * Cin * MEAN_M)), (1, 1, 1), _unit_ints).reshape(5, 5, 5, Cin, Co)
+        dy = _sparse(rng, ys, min(1.0, budget * 1.4 / (M * MEAN_M)), brick, _unit_ints)
+    elif profile == "mid-dense-w":                        # w two-piece everywhere; x and dy integers
+        w = _deep2(rng, (5, 5, 5, Cin, Co))
+        x = _sparse(rng, xs, min(1.0, budget * 1.4 / (125 * Cin * MEAN_M)), brick, _unit_ints)
+        dy = _sparse(rng, ys, min(1.0, budget * 1.4 / (125 * Co * MEAN_M)), brick, _unit_ints)
+    elif profile == "mid-mid":                            # all two-piece (k < 2^9): x a share of the tile, w the cover filter, dy sparse
+        mm = (1.5 * 2.0 ** 8) ** 2                        # units of one mm product
+        two = lambda r, n: _two_piece(r, n, 9) * 2.0 ** -Q2
+        p = float(min(1.0, budget / (nfw * mm)))
+        x = _deep2(rng, xs, p, 9)
+        w = _filter_cover(rng, Cin, Co, two)
+        ndy = budget / (p * mm + 2 * 1.5 * 2.0 ** 8)
+        dy = _cover(rng, ys, ndy, brick, two)
+    else:
+        raise KeyError(profile)
+    return dict(x=x, w=w, dy=dy, b=_ints(rng, 3, (Co,)))
+
+
+def bound_x3(c, d, profile):
+    """(E2): {output: max over its elements of sum |a| |b| in the output's own unit} -- the oracle on magnitudes.  db is left out where
+    dy is the dense deep operand (it is no f32x3 product and is held to a counted bound instead)."""
+    qx, qw, qdy = (QOF[k] for k in DEPTHS[profile])
+    m = exact(c, d, magnitude=True)
+    out = {"y": np.abs(m["y"]).max() * 2.0 ** (qx + qw), "dw": np.abs(m["dw"]).max() * 2.0 ** (qx + qdy),
+           "dx": max(np.abs(m["dx0"]).max(), np.abs(m["dx1"]).max() if m["dx1"].size else 0.0) * 2.0 ** (qdy + qw)}
+    if profile != "dy-deep":
+        out["db"] = np.abs(m["db"]).max() * 2.0 ** qdy
+    return out
+
+
+THINS = tuple(0.75 ** i for i in range(16))
+
+
+@functools.lru_cache(4)
+def operands_x3(c, profile):
+    """The operands of (case, profile): the design sizes, thinned until every output's magnitude sum is below 2^24 units.  The dict
+    carries 'thin' and 'bound' (bound_x3 of the operands returned)."""
+    for thin in THINS:
+        d = _draw_x3(c, profile, thin)
+        b = bound_x3(c, d, profile)
+        if max(b.values()) < X3_LIMIT:
+            d["thin"], d["bound"] = thin, b
+            return d
+    raise AssertionError("%s %s: no thinning keeps the magnitude sums below 2^24 units" % (c.cid, profile))
+
+
+def check_e1(d, profile):
+    """(E1) from the restated split: the split reproduces every operand exactly within its depth, and in each launch (x, w), (dy, w),
+    (x, dy) no m meets an l and no l an l.  Returns {operand: (h, m, l)}."""
+    pieces = {}
+    for name, depth in zip(("x", "w", "dy"), DEPTHS[profile]):
+        h, m, l = split3_np(d[name])
+        assert np.array_equal(h + m + l, d[name]) and np.array_equal(d[name].astype(np.float32).astype(np.float64), d[name]), name
+        k = d[name] * 2.0 ** QOF[depth]
+        assert np.array_equal(k, np.round(k)), (name, "not a whole number of units")
+        assert depth >= 3 or not l.any(), (name, "l piece in a depth-%d operand" % depth)
+        assert depth >= 2 or not m.any(), (name, "m piece in a depth-1 operand")
+        pieces[name] = (h, m, l)
+    for a, b in (("x", "w"), ("dy", "w"), ("x", "dy")):
+        (_, ma, la), (_, mb, lb) = pieces[a], pieces[b]
+        assert not (ma.any() and lb.any()) and not (la.any() and mb.any()) and not (la.any() and lb.any()), (a, b)
+    return pieces
+
+
+def colsum_roundings(M, C):
+    """fp32 roundings on the longest path of one element through the bias gradient ops.conv's backward calls (csrc/elementwise.hip
+    vnet_colsum): colsum_vec_kernel -- a thread adds its trips (the first add, to 0, is exact), block_reduce_vec halves 256 threads down
+    to C / 4 -- or, where C / 4 is no power of two, colsum_generic_kernel -- one shared-memory atomicAdd chain per channel and block;
+    then sum_finalize_kernel sums the blocks' rows in float64 and rounds once."""
+    if C % 4 == 0 and (C // 4) & (C // 4 - 1) == 0 and C // 4 <= 256:
+        nq = M * (C // 4)
+        nblk = max(1, min(1024, cdiv(nq // 4 + 1, 256)))
+        trips = cdiv(nq, nblk * 256)
+        return (trips - 1) + (256 // (C // 4)).bit_length() - 1 + 1
+    nblk = max(1, min(1024, cdiv(M * C // 4 + 1, 256)))
+    return cdiv(M * C, nblk * 256) * (256 // C + 1) + 1         # (a trip's 256 consecutive elements hold at most 256 // C + 1 of a channel)
+
+
+def x3_table(rows):
+    """The case-by-profile table of profiles/conv_sweep.txt.  rows: [(case, profile, dict(seconds, bound, m, l, empty, thin))]."""
+    out = ["%-44s %-12s %5s %9s %6s %6s %6s %7s" % ("case", "profile", "thin", "bound/2^24", "m!=0", "l!=0", "empty", "seconds")]
+    for c, p, r in rows:
+        out.append("%-44s %-12s %5.2f %9.3f %6.3f %6.3f %6.3f %7s" % (c.cid, p, r["thin"], r["bound"] / X3_LIMIT, r["m"], r["l"], r["empty"],
+                                                                      "%.2f" % r["seconds"] if "seconds" in r else "-"))
+    return "\n".join(out)
 
 
 # ---- routing --------------------------------------------------------------------------------------------------------------------

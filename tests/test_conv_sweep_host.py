@@ -1,7 +1,9 @@
 """Host-side checks of the exact-integer convolution sweep (tests/conv_sweep.py): the coverage conditions of the generated case
 set, stated as code; the identity of the float64 torch oracle and oracle/vnet_oracle.py on integer operands, which the GPU
 comparison rests on; the 2^20 exactness guard of every case; the restated C planners against the library's shape-only queries; and
-ops.route()'s family for every launch of every case, so that a routing change fails here and does not silently empty the sweep."""
+ops.route()'s family for every launch of every case, so that a routing change fails here and does not silently empty the sweep.
+For the operand profiles of the f32x3 rows (S.PROFILES): the split identity, the two exactness conditions, the piece shares, the
+coverage of sparse filters and of the filter gradient's bricks, and a float32 restatement of the six product streams."""
 import collections
 
 import numpy as np
@@ -186,3 +188,161 @@ def test_class_pairs_the_each_choice_design_covers():
         for (a, b), (have, total) in d.items():
             n = max(len(S.classes_of(S.VARIANTS[name], a)), len(S.classes_of(S.VARIANTS[name], b)))
             assert min(n, total) <= have <= total, (name, a, b, have, total)
+
+
+# ---- the operand profiles of the f32x3 rows (S.PROFILES): operands that fill the m and l pieces, still compared with `==` ------------
+X3_CASES = S.x3_cases()
+X3_RUNS = S.x3_runs()
+# the sparse operand(s) of the filter-gradient launch (x, dy), per profile
+WGRAD_SPARSE = {"x-deep": ("dy",), "w-deep": ("x", "dy"), "dy-deep": ("x",), "mid-dense-x": ("dy",), "mid-dense-w": ("x", "dy"), "mid-mid": ("dy",)}
+COVER_FILTER = ("x-deep", "dy-deep", "mid-mid")                  # profiles whose filter is the sparse side of both convolution launches
+EMPTY_CAP = 0.25
+
+
+def x3_conditions(c, profile):
+    """Every host condition of one (case, profile); returns the figures of its row in profiles/conv_sweep.txt."""
+    d = S.operands_x3(c, profile)
+    pieces = S.check_e1(d, profile)                               # the split identity and (E1)
+    b = d["bound"]                                                # (E2): bound_x3 of these very operands, the oracle on magnitudes
+    assert max(b.values()) < S.X3_LIMIT, (c.cid, profile, b)
+    assert ("db" in b) == (profile != "dy-deep")
+    assert np.array_equal(d["b"], np.round(d["b"]))
+    row = dict(thin=d["thin"], bound=max(b.values()), m=0.0, l=0.0, empty=0.0)
+    deep = S.DEEP.get(profile)
+    if deep:
+        a, (h, m, l) = d[deep], pieces[deep]
+        row["m"], row["l"] = float((m != 0).mean()), float((l != 0).mean())
+        assert row["m"] >= S.M_FLOOR, (c.cid, profile, row)
+        assert row["l"] >= S.l_floor(c, profile), (c.cid, profile, row, S.l_floor(c, profile))
+        for piece in (a, h, m) + ((l,) if S.DEPTHS[profile][("x", "w", "dy").index(deep)] == 3 else ()):
+            assert (piece > 0).any() and (piece < 0).any(), (c.cid, profile)
+        assert a.all(), "the deep operand of %s is dense" % profile
+    else:                                                         # mid-mid: every operand carries second pieces of both signs
+        for name in ("x", "w", "dy"):
+            m = pieces[name][1]
+            assert (m > 0).any() and (m < 0).any(), (c.cid, name)
+        row["m"] = float((pieces["x"][1] != 0).mean())
+    if profile in COVER_FILTER:
+        nz = d["w"].reshape(125, c.C0 + c.C1, c.O) != 0
+        assert nz.any(2).all(), "%s %s: a (tap, input channel) without a weight" % (c.cid, profile)
+        assert nz.any(1).all(), "%s %s: a (tap, output channel) without a weight" % (c.cid, profile)
+    else:
+        assert (np.abs(d["w"]).reshape(125, -1).max(1) > 0).all()
+    p = S.x3_wgrad_plan(c.C0 + c.C1, c.O, c.B, c.D, c.H, c.W)
+    assert p.brick == c.v.brick(c.W) and p.nb == S._bricks_of((c.B,) + c.dims, p.brick)
+    row["empty"] = max(S.empty_bricks(d[name], p.brick) for name in WGRAD_SPARSE[profile])
+    if row["empty"] > 0:
+        print("%s %s: %.1f %% of the %d bricks hold no non-zero of the sparse operand" % (c.cid, profile, 100 * row["empty"], p.nb))
+    assert row["empty"] <= EMPTY_CAP, (c.cid, profile, row)
+    if c.v.launch == "wgrad":                                     # (the filter-gradient rows are small: (E2) leaves room for every brick)
+        assert row["empty"] == 0.0, (c.cid, profile, row)
+    return row
+
+
+@pytest.mark.parametrize("case", X3_CASES, ids=lambda c: c.cid)
+def test_x3_profiles_hold_their_conditions(case):
+    """Per (case, profile): the restated split reproduces every operand, (E1) and (E2) hold, the deep operand has m != 0 in >= 90 % and
+    l != 0 in >= l_floor (20 %, or what (E2) leaves at that channel ratio) of its elements with both signs in every piece, a sparse
+    filter uses every (tap, input channel) and every (tap, output channel), and the sparse operand of the filter gradient reaches
+    every brick of x3_wgrad_plan's tiling (at most 25 % empty, none on the filter-gradient rows)."""
+    profiles = [p for c, p in X3_RUNS if c == case]
+    assert set(("x-deep", "w-deep", "dy-deep")) <= set(profiles)
+    for profile in profiles:
+        x3_conditions(case, profile)
+
+
+def test_x3_runs_keep_every_profile_on_every_row():
+    """The deep profiles run on every f32x3 case; the mid-dense and mid-mid profiles on the most ragged case of each of the seven rows."""
+    assert set(X3_RUNS) <= set((c, p) for c in X3_CASES for p in S.PROFILES)
+    for name in set(c.variant for c in X3_CASES):
+        for p in S.PROFILES:
+            cs = [c for c, q in X3_RUNS if q == p and c.variant == name]
+            assert cs, (name, p)
+            if p.startswith("mid"):
+                n = sum(k in S.RAGGED for k in S.case_classes(cs[0]))
+                assert len(cs) == 1 and n == (2 if name.endswith("narrow") else 3), (name, p, cs)
+            else:
+                assert len(cs) == len(BY_VARIANT[name])
+
+
+def test_x3_profiles_reach_every_stream():
+    """Over the profiles, each of the three launches multiplies non-zero pieces in each of the six streams."""
+    for ia, ib in ((0, 1), (2, 1), (0, 2)):                      # (x, w), (dy, w), (x, dy)
+        reached = set()
+        for dep in S.DEPTHS.values():
+            reached |= set((pa, pb) for pa in range(dep[ia]) for pb in range(dep[ib]))
+        assert reached >= {(0, 0), (0, 1), (1, 0), (1, 1), (0, 2), (2, 0)}, (ia, ib, reached)
+
+
+def _smallest_x3(n=3):
+    best = {}
+    for c in X3_CASES:
+        k = c.B * c.D * c.H * c.W * (c.C0 + c.C1) * c.O
+        if c.variant not in best or k < best[c.variant][0]:
+            best[c.variant] = (k, c)
+    return [c for _, c in sorted(best.values(), key=lambda t: t[0])[:n]]
+
+
+def _patches(a):
+    """[voxels, 125 * C] SAME-padded 5^3 patches of a [B, D, H, W, C] tensor (tap-major, as a [5, 5, 5, C, .] filter reshapes)."""
+    B, D, H, W, C = a.shape
+    p = np.pad(a, ((0, 0), (2, 2), (2, 2), (2, 2), (0, 0)))
+    v = np.lib.stride_tricks.sliding_window_view(p, (5, 5, 5), axis=(1, 2, 3))          # [B, D, H, W, C, 5, 5, 5]
+    return np.ascontiguousarray(np.moveaxis(v, 4, 7)).reshape(B * D * H * W, 125 * C)
+
+
+STREAMS = ((0, 0), (0, 1), (1, 0), (1, 1), (0, 2), (2, 0))
+
+
+def _emulate(A, Bm, drop=None):
+    """sum_k A[n, k] B[k, o] from the six streams of the pieces, every product and every partial sum in float32, in three orders:
+    sequential, sequential over a random permutation of the (stream, k) terms, numpy's pairwise reduction (with a stream dropped:
+    the pairwise one only).  A, Bm: piece triples; streams whose pieces are all zero add exact zeros and are left out."""
+    live = [(pa, pb) for s, (pa, pb) in enumerate(STREAMS) if s != drop and A[pa].any() and Bm[pb].any()]
+    if not live:
+        return [np.zeros((A[0].shape[0], Bm[0].shape[1]), np.float32)]
+    terms = np.concatenate([A[pa].astype(np.float32)[:, :, None] * Bm[pb].astype(np.float32)[None, :, :] for pa, pb in live], axis=1)
+    assert terms.dtype == np.float32
+    if drop is not None:
+        return [terms.sum(axis=1, dtype=np.float32)]
+    seq = lambda t: np.add.accumulate(t, axis=1, dtype=np.float32)[:, -1]
+    return [seq(terms), seq(terms[:, np.random.default_rng(7).permutation(terms.shape[1])]), terms.sum(axis=1, dtype=np.float32)]
+
+
+@pytest.mark.parametrize("profile", S.PROFILES)
+@pytest.mark.parametrize("case", _smallest_x3(), ids=lambda c: c.cid)
+def test_x3_six_stream_emulation_equals_the_oracle(case, profile):
+    """The kernels' arithmetic restated in float32 -- six streams of piece products, summed in three orders -- equals the float64
+    oracle bit for bit on the profile's operands (what the GPU `==` rests on), for y, dx and one tap plane of dw; and leaving out any
+    one stream the profile's depths reach changes the result, so no reachable stream is multiplying zeros."""
+    d = S.operands_x3(case, profile)
+    pc = S.check_e1(d, profile)
+    e = S.exact(case, d)
+    Cin, Co = case.C0 + case.C1, case.O
+    dx = np.concatenate((e["dx0"], e["dx1"]), -1)
+    wf = lambda a: a.reshape(125 * Cin, Co)
+    wb = lambda a: np.ascontiguousarray(a[::-1, ::-1, ::-1].transpose(0, 1, 2, 4, 3)).reshape(125 * Co, Cin)
+    dx_, dw_ = ("dy", "w"), ("x", "dy")
+    jobs = [("y", tuple(_patches(p) for p in pc["x"]), tuple(wf(p) for p in pc["w"]), e["y"].reshape(-1, Co) - d["b"], (0, 1)),
+            ("dx", tuple(_patches(p) for p in pc["dy"]), tuple(wb(p) for p in pc["w"]), dx.reshape(-1, Cin), (2, 1)),
+            # dw[tap 62 (the centre), ci, co] = sum_v x[v, ci] dy[v, co]
+            ("dw", tuple(p.reshape(-1, Cin).T for p in pc["x"]), tuple(p.reshape(-1, Co) for p in pc["dy"]), e["dw"].reshape(125, Cin, Co)[62], (0, 2))]
+    dep = S.DEPTHS[profile]
+    for name, A, Bm, want, (ia, ib) in jobs:
+        for got in _emulate(A, Bm):
+            assert np.array_equal(got.astype(np.float64), want), (case.cid, profile, name)
+        for s, (pa, pb) in enumerate(STREAMS):
+            if pa < dep[ia] and pb < dep[ib]:
+                assert not np.array_equal(_emulate(A, Bm, drop=s)[0].astype(np.float64), want), (case.cid, profile, name, "stream", s)
+            else:
+                assert not A[pa].any() or not Bm[pb].any(), (case.cid, profile, name, s)
+
+
+def test_colsum_roundings_counts_the_vector_and_the_generic_kernel():
+    """The counted bound of the dy-deep bias gradient: trips - 1 + log2(256 / (C / 4)) + 1 roundings in the vector kernel, the atomic
+    chain of a block + 1 in the generic one (C / 4 no power of two: the 48-channel cases)."""
+    assert S.colsum_roundings(1024, 16) == 3 + 6 + 1                      # 4096 float4 on 5 blocks (a block per 1024): 4 trips
+    assert S.colsum_roundings(1024 * 256 * 3, 16) == 11 + 6 + 1           # the grid cap, 1024 blocks: 12 trips
+    assert S.colsum_roundings(1024, 32) == 3 + 5 + 1
+    assert S.colsum_roundings(64, 48) == 3 * (256 // 48 + 1) + 1          # 3072 elements on 4 blocks: 3 trips of <= 6 of a channel
+    assert any(c.O == 48 for c in X3_CASES) and any(c.O in (16, 32) for c in X3_CASES)

@@ -42,7 +42,25 @@ of the mutated family against the same mutated library:
     IS the c16pp kernel.  No b16-c16 case (BF16_C16PP = 0) and no case with W = 16k failed.
     Existing tests: caught as well (test_hip_b16.py, 4 failed: the 30x50x70 and 33x40x49 shapes of CONV5_SHAPES, one statistics case, the
     c16 / c16pp bit-identity test).  The expectation that the hand-picked lists miss a one-column mask error did not hold for this kernel:
-    check_bf16 forgives 0.5 % of unlucky roundings, but no wrong value."""
+    check_bf16 forgives 0.5 % of unlucky roundings, but no wrong value.
+
+ALL THREE PIECES OF THE f32x3 SPLIT (test_conv_sweep_x3_pieces).  Integer operands are bf16-exact: m = l = 0, so the tests above hold the
+index math of the h plane only.  The seven f32x3 rows run again under the operand profiles of tests/conv_sweep.py (x-deep, w-deep,
+dy-deep on every case; mid-dense-x, mid-dense-w, mid-mid on the most ragged case of each row): 18-bit and 9-10-bit operands that put
+non-zero values into the m and l tile images, the m / l filter pieces and all six product streams, sized per case so that every
+partial sum stays below 2^24 units -- y, dx0, dx1, dw (and db, except under dy-deep: a counted rounding bound) are still `==` the
+float64 oracle.  Measured on one MI355X in one session, inside the whole -m gpu suite: the suite 350.8 s wall; these 174 tests 82.5 s;
+all other tests, i.e. the parent's suite, 256.2 s (a quarter: 64 s).  All 306 (case, profile) pairs took 145 s and passed; being over
+a quarter, the three mid profiles were thinned to one case per row as the sweep's rule says, the deep profiles were not (3 x 51
+tests, 77 s).  The time is the host's float64 oracle, twice per test; the slowest test takes 4.3 s.
+Mutations (value only; each one build, one run of the new tests and of test_hip_x3.py, the integer f32x3 rows, test_hip_insitu_backward.py,
+test_hip_golden_full.py; details in profiles/conv_sweep.txt):
+ 1. conv_x3.h tile_commit writes 0 for the l piece of the last tile row: 18 new tests failed (x-deep and dy-deep of the nine cases
+    whose last halo row lies inside the volume).  Parent: missed, all 103 tests passed.
+ 2. x3_pack.h / the batched repack write 0 for the l piece of pair 62, tap (4, 4, 4): 36 new tests failed, all w-deep.  Parent: every
+    test that runs a kernel passed; test_hip_x3.py::test_x3_split_is_exact, which adds up the packed image itself, failed.
+ 3. conv_x3.h wgrad commit leaves the m piece of -dy un-negated in the negated bricks: 17 new tests failed (dy-deep and mid-mid of the
+    cases with more bricks than filter-gradient workgroups).  Parent: caught, test_hip_x3.py 9 failed."""
 import contextlib
 
 import numpy as np
@@ -213,6 +231,58 @@ def test_conv_sweep(dev, case, lib_option, monkeypatch):
     with contextlib.ExitStack() as stack:
         S.force(case, lib_option, monkeypatch, stack)
         {"pair": _run_pair, "input": _run_input}.get(case.v.op, _run_conv)(case, dev, d, e)
+
+
+# ---- the f32x3 rows again, on operands that fill all three pieces (S.PROFILES; proved on the host by test_conv_sweep_host.py) ----
+X3 = S.x3_runs()
+
+
+def _db_bounded(case, got, d, exact):
+    """The bias gradient where dy is dense and three pieces deep: a column sum, no f32x3 product, whose terms exceed 2^24 units -- held
+    per channel to k * 2^-24 * sum |dy| with k the roundings on an element's longest path (S.colsum_roundings), as tier B of
+    tests/ew_sweep.py (gamma_k = k u / (1 - k u))."""
+    M = case.B * case.D * case.H * case.W
+    k = S.colsum_roundings(M, case.O)
+    u = 2.0 ** -24
+    lim = k * u / (1 - k * u) * np.abs(d["dy"]).reshape(-1, case.O).sum(0)
+    err = np.abs(got.detach().cpu().double().numpy() - exact)
+    print("%s db: k = %d, max err / bound = %.3g" % (case.cid, k, float((err / lim).max())))
+    assert (err <= lim).all(), "%s db: error %s above the counted bound %s (k = %d)" % (case.cid, err, lim, k)
+
+
+@pytest.mark.parametrize("case,profile", X3, ids=lambda v: v if isinstance(v, str) else v.cid)
+def test_conv_sweep_x3_pieces(dev, case, profile, lib_option, monkeypatch):
+    """One f32x3 case under one operand profile: forward and backward through ops.conv in the guarded arena, y, dx0, dx1 and dw `==`
+    the float64 oracle (db too, except under dy-deep: _db_bounded), all three launches on the f32x3 kernels.  No statistics launch."""
+    from vnet_tensorflow_amd import ops
+    d = S.operands_x3(case, profile)
+    S.check_e1(d, profile)
+    assert max(d["bound"].values()) < S.X3_LIMIT
+    e = S.exact(case, d)
+    brick = case.v.brick(case.W)
+    with contextlib.ExitStack() as stack:
+        S.force(case, lib_option, monkeypatch, stack)
+        with _arena(dev) as h:
+            tx0 = h.g(d["x"][..., :case.C0]).requires_grad_(True)
+            tx1 = h.g(d["x"][..., case.C0:]).requires_grad_(True) if case.C1 else None
+            tw, tb = h.g(d["w"]).requires_grad_(True), h.g(d["b"]).requires_grad_(True)
+            ops.profile_start()
+            try:
+                y = ops.conv(tx0, tw, tb, 5, 1, x1=tx1)
+                y.backward(h.g(d["dy"]))
+            finally:
+                recs = [r[0] for r in ops.profile_stop()]
+            assert sum(1 for t in recs if t.startswith("conv-x3")) == 2, recs           # forward and backward-data
+            assert sum(1 for t in recs if t.startswith("wgrad-x3")) == 1, recs          # and the filter gradient
+            _equal(case, "y", y, e["y"], brick)
+            _equal(case, "dx0", tx0.grad, e["dx0"], brick)
+            if case.C1:
+                _equal(case, "dx1", tx1.grad, e["dx1"], brick)
+            _equal(case, "dw", tw.grad, e["dw"])
+            if profile == "dy-deep":
+                _db_bounded(case, tb.grad, d, e["db"])
+            else:
+                _equal(case, "db", tb.grad, e["db"])
 
 
 # ---- the grouped bf16 filter gradient (vnet_conv_wgrad_b16_group) through tests/test_hip_wgrad_group.py's helper -----------------
