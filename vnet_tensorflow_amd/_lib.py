@@ -1,5 +1,6 @@
 """ctypes binding of libvnet_hip.so (include/vnet_hip.h, include/vnet_hip_unet.h, include/vnet_hip_head.h,
-include/vnet_hip_resample.h, include/vnet_hip_components.h, include/vnet_hip_deform.h, include/vnet_hip_sample.h).
+include/vnet_hip_resample.h, include/vnet_hip_components.h, include/vnet_hip_deform.h, include/vnet_hip_sample.h,
+include/vnet_hip_prepare.h).
 
 The library is the product: there is NO fallback.  If the shared object is missing, or a
 kernel reports an error, this module raises -- nothing silently routes to PyTorch or the CPU.
@@ -171,6 +172,15 @@ SIGNATURES_SAMPLE = {
     "vnet_sample_patch": (_i, [_vp, _vp, _vp, _vp] + [_i] * 11 + [_f, _u64, _vp]),
 }
 
+# eighth public header, include/vnet_hip_prepare.h (a case of evaluate on the device: statistics, intensity window, crop, argmax)
+SIGNATURES_PREPARE = {
+    "vnet_channel_stats_ws_bytes": (_sz, [_i]),
+    "vnet_channel_stats": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _sz, _vp]),
+    "vnet_window_intensity": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
+    "vnet_crop_words": (_i, [_vp, _vp] + [_i] * 10 + [_vp]),
+    "vnet_argmax_label": (_i, [_vp, _vp, _i64, _i, _vp]),
+}
+
 
 class WgradJob(ctypes.Structure):
     """include/vnet_hip.h: vnet_wgrad_job (one layer of vnet_conv_wgrad_b16_group)."""
@@ -229,10 +239,11 @@ def lib():
             elif name.endswith("_ws_bytes") or name.endswith("_stats_rows") or name == "vnet_conv_stats_from_reduce" or name == "vnet_packed_weight_floats":
                 setattr(L, name, _memo(fn))    # pure size queries, asked before every launch: answer repeats from a dict
         for name, (res, args) in list(SIGNATURES_UNET.items()) + list(SIGNATURES_HEAD.items()) + list(SIGNATURES_RESAMPLE.items()) + \
-                list(SIGNATURES_COMPONENTS.items()) + list(SIGNATURES_DEFORM.items()) + list(SIGNATURES_SAMPLE.items()):
+                list(SIGNATURES_COMPONENTS.items()) + list(SIGNATURES_DEFORM.items()) + list(SIGNATURES_SAMPLE.items()) + list(SIGNATURES_PREPARE.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
-            if name in ("vnet_bn_head_ok", "vnet_bn_head_stats_rows", "vnet_bn_head_ws_bytes", "vnet_cc_ws_bytes", "vnet_cc_table_ws_bytes"):
+            if name in ("vnet_bn_head_ok", "vnet_bn_head_stats_rows", "vnet_bn_head_ws_bytes", "vnet_cc_ws_bytes", "vnet_cc_table_ws_bytes",
+                        "vnet_channel_stats_ws_bytes"):
                 setattr(L, name, _memo(fn))
         _lib = L
     return _lib

@@ -331,6 +331,9 @@ class image2label(object):
         self.evaluate_lcc = E.get('LargestConnectedComponent', False)
         self.evaluate_volume_threshold = E.get('VolumeThreshold', False)
         self.evaluate_pipeline = E.get('Pipeline')
+        # extension (opt-in): the evaluate pipeline and the window crops on a case uploaded once (prepare.prepare_on_device, DESIGN
+        # section 6e).  Off by default: the device sums a channel's statistics in another order than NumPy
+        self.prepare_on_device = bool(E.get('PrepareOnDevice', False))
         self._print("{}: Reading configuration file complete".format(_now()))
 
     # -- reference model.py:297-630 (network + loss head; summaries/metrics not carried) ---------------
@@ -970,7 +973,11 @@ class image2label(object):
         is copied out -- the largest face-connected component first, then the threshold on its 0/1 result, `spacing` the voxel size
         of the grid the label is returned on.  They see the volume the caller gets: on the back_size branch the resampled label, else
         the label cropped to images_np's extent, and to `extent` where that is smaller (evaluate(): the input file's size, which a
-        Padding transform may have grown).  The label is then the 0/1 map.  With neither filter nothing changes."""
+        Padding transform may have grown).  The label is then the 0/1 map.  With neither filter nothing changes.
+        images_np may also be a float32 tensor [X,Y,Z,Cin] on the model's device (a case prepared there, prepare.prepare_on_device):
+        the same windows in the same batches, each cut on the device by ops.crop_window into its slot of the batch -- no worker
+        threads, no pinned staging, no prepare_batch -- and the label formed by ops.argmax_label.  The results are NumPy arrays with
+        the values of the array path."""
         vt = volume_threshold if volume_threshold is not None and volume_threshold > 0 else None
         filtered = bool(largest_component) or vt is not None
         sp = tuple(float(v) for v in spacing) if spacing is not None else (1.0, 1.0, 1.0)
@@ -981,10 +988,20 @@ class image2label(object):
             return ops.volume_threshold(label, vt, sp)
         ps, st = list(self.patch_shape), list(self.evaluate_stride)
         pads = [(0, max(p - s, 0)) for s, p in zip(images_np.shape[:3], ps)]
-        orig = images_np.shape[:3]
-        if any(hi for _, hi in pads):
-            images_np = np.pad(images_np, pads + [(0, 0)])
-        dims = images_np.shape[:3]
+        orig = tuple(int(v) for v in images_np.shape[:3])
+        resident = isinstance(images_np, torch.Tensor)
+        if resident:
+            # the case lives in device memory: every window is cut there (ops.crop_window writes zeros where a window reaches past
+            # the volume, which is the np.pad below without the padded copy), and the label is formed there as int32
+            if images_np.dim() != 4 or images_np.dtype != torch.float32 or images_np.device != self.device:
+                raise VnetHipError("evaluate_single_3D: a device case is a float32 [X,Y,Z,Cin] tensor on %s, got %s %s on %s" % (
+                    self.device, images_np.dtype, tuple(images_np.shape), images_np.device))
+            images_np = images_np.contiguous()
+            dims = tuple(max(s, p) for s, p in zip(orig, ps))
+        else:
+            if any(hi for _, hi in pads):
+                images_np = np.pad(images_np, pads + [(0, 0)])
+            dims = images_np.shape[:3]
         nums = [int(math.ceil((dims[a] - ps[a]) / float(st[a]))) + 1 for a in range(3)]
         batches, tmp, patch_total = [], [], 0
         for i in range(nums[0]):
@@ -1012,6 +1029,18 @@ class image2label(object):
             t = torch.from_numpy(prepare_batch(bd))
             return (t.pin_memory() if self.device.type == "cuda" else t), torch.zeros(1, dtype=torch.int32)
 
+        if resident:
+            # one stream, one slot: the crops of a batch are enqueued behind the network's reads of the batch before it
+            slot = torch.empty((max(len(bd['indexes']) for bd in batches),) + tuple(ps) + (images_np.shape[3],),
+                               dtype=torch.float32, device=self.device)
+            for bd in batches:
+                batch = slot[:len(bd['indexes'])]
+                for j, idx in enumerate(bd['indexes']):
+                    ops.crop_window(images_np, (idx[0], idx[2], idx[4]), ps, out=batch[j])
+                sm = self._infer(batch)
+                for j, idx in enumerate(bd['indexes']):
+                    ops.accumulate_patch(sm[j], vol, cnt, (idx[0], idx[2], idx[4]))
+            return self._device_case_results(vol, cnt, orig, back_size, back_ratio, filters if filtered else None, extent)
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=int(getattr(self, "loader_threads", 3))) as pool:
             def windowed(depth=3):
@@ -1056,6 +1085,33 @@ class image2label(object):
         softmax_np = np.moveaxis(vol_np, -1, 0) / np.float32(cnt_np)          # model.py:935-937
         return label_np[sl], softmax_np[(slice(None),) + sl]
 
+    def _device_case_results(self, vol, cnt, orig, back_size, back_ratio, filters, extent):
+        """What evaluate_single_3D returns for a case that lives in device memory, from the summed softmax `vol` and the count map
+        `cnt`: the same values as the array path's tail above.  The label is formed by ops.argmax_label as int32 (no int64 volume,
+        no cast pass), cropped on the device, and comes down once."""
+        label = ops.argmax_label(vol)
+        sl = tuple(slice(0, s) for s in orig)
+        if back_size is not None:
+            label = ops.resample(label, back_size, back_ratio, "nearest")
+            if filters is not None:
+                label = filters(label)
+            label_np = label.cpu().numpy().astype(np.int64)
+            if not self.evaluate_probability_output:
+                return label_np, None
+            prob = ops.resample(vol, back_size, back_ratio, "linear", divisor=cnt)
+            return label_np, np.moveaxis(prob.cpu().numpy(), -1, 0)
+        # (the filters see the volume cropped to the input file's extent, as on the array path)
+        keep = tuple(orig) if filters is None else tuple(min(s, e) for s, e in zip(orig, extent if extent is not None else orig))
+        if keep != tuple(int(v) for v in label.shape):
+            label = ops.crop_window(label, (0, 0, 0), keep)
+        if filters is not None:
+            label = filters(label)
+        label_np = label.cpu().numpy().astype(np.int64)
+        if not self.evaluate_probability_output:
+            return label_np, None
+        vol_np, cnt_np = vol.cpu().numpy(), cnt.cpu().numpy()
+        return label_np, (np.moveaxis(vol_np, -1, 0) / np.float32(cnt_np))[(slice(None),) + sl]
+
     # -- reference model.py:1131-1242 ------------------------------------------------------------------------------
     @in_context
     def evaluate(self):
@@ -1087,17 +1143,29 @@ class image2label(object):
             on_device = {}
             if self.evaluate_lcc or vt is not None:
                 on_device = dict(largest_component=bool(self.evaluate_lcc), volume_threshold=vt, spacing=spacing, extent=chans[0].shape)
+            prepared = None
+            if tf is not None and self.prepare_on_device and self.device.type == "cuda":
+                # EvaluationSetting.PrepareOnDevice: the file goes up once, the pipeline and the window crops run there (None: the
+                # pipeline holds a transform the device path does not serve, and the host path below is kept)
+                from . import prepare as vprep
+                prepared = vprep.prepare_on_device(tf, torch.from_numpy(image).to(self.device), spacing)
+            if prepared is not None:
+                case, _, case_spacing = prepared
+            elif regrid:
+                sample = vtf.run_pipeline(tf, {'image': image, 'label': np.zeros(image.shape[:3], dtype=np.int32), 'spacing': spacing},
+                                          np.random.default_rng(0))
+                case, case_spacing = sample['image'], sample['spacing']
+            else:
+                case = image
+                if tf is not None:
+                    case, _ = vtf.apply_pipeline(tf, image, np.zeros(image.shape[:3], dtype=np.int32), np.random.default_rng(0))
             if regrid:
                 # the pipeline changes the grid: window on the transformed grid, then back to the input file's size and spacing
                 # (model.py:939-975) before the label filters below, which work in the input's physical units
-                sample = vtf.run_pipeline(tf, {'image': image, 'label': np.zeros(image.shape[:3], dtype=np.int32), 'spacing': spacing},
-                                          np.random.default_rng(0))
-                label, softmax = self.evaluate_single_3D(sample['image'], back_size=chans[0].shape,
-                                                         back_ratio=vrs.ratios(sample['spacing'], spacing), **on_device)
+                label, softmax = self.evaluate_single_3D(case, back_size=chans[0].shape,
+                                                         back_ratio=vrs.ratios(case_spacing, spacing), **on_device)
             else:
-                if tf is not None:
-                    image, _ = vtf.apply_pipeline(tf, image, np.zeros(image.shape[:3], dtype=np.int32), np.random.default_rng(0))
-                label, softmax = self.evaluate_single_3D(image, **on_device)
+                label, softmax = self.evaluate_single_3D(case, **on_device)
                 label = label[tuple(slice(0, n) for n in chans[0].shape)]
                 if softmax is not None:
                     softmax = softmax[(slice(None),) + tuple(slice(0, n) for n in chans[0].shape)]

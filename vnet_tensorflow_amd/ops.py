@@ -1885,6 +1885,97 @@ def sample_patch(image, label, start, patch, flip, sigma, seed, out_image, out_l
               "vnet_sample_patch")
 
 
+# ---- a case of evaluate on the device (include/vnet_hip_prepare.h; rules: vnet_tensorflow_amd/prepare.py) -------------------------
+# No autograd.  They launch on torch's current stream of the calling thread, like resample.
+STATS_MAX_BLOCKS = 1024    # VNET_STATS_MAX_BLOCKS: a channel's voxels are spread over at most this many blocks of 256 threads
+
+
+def _channels_last(x, what):
+    """(n, C) of a dense float32 device tensor [..., C] with at least one voxel."""
+    _need_gpu(x, what)
+    if x.dim() < 2 or x.numel() == 0 or not x.is_contiguous():
+        raise VnetHipError("%s: takes a dense, non-empty [..., C] tensor, got %s" % (what, tuple(x.shape)))
+    C = int(x.shape[-1])
+    return x.numel() // C, C
+
+
+def _rows(t, C, width, device, what):
+    """A per-channel parameter table as the kernels take it: float64 [C, width] on `device` (anything torch.as_tensor takes is uploaded)."""
+    if not (isinstance(t, torch.Tensor) and t.device == device and t.dtype == torch.float64):
+        t = torch.as_tensor(t, dtype=torch.float64).to(device)
+    if tuple(t.shape) != (C, width):
+        raise VnetHipError("%s: expected a [%d, %d] table, got %s" % (what, C, width, tuple(t.shape)))
+    return t.contiguous()
+
+
+def channel_stats(image, pre=None):
+    """Per-channel statistics of a float32 device tensor [..., C]: a float64 device tensor [C, 4] = {sum, css, min, max} of
+    v = (x - a) / b in double, pre = [C, 2] rows {a, b} (None: v = x); css = sum (v - sum / n)^2, the mean formed on the device.
+    Summed in a fixed order that differs from NumPy's pairwise one: equal to it where the sums are exact, else within rounding."""
+    n, C = _channels_last(image, "channel_stats")
+    L = _lib.lib()
+    need = L.vnet_channel_stats_ws_bytes(C)
+    if need == 0:
+        raise VnetHipError("channel_stats: %d channels (at most 65535)" % C)
+    if pre is not None:
+        pre = _rows(pre, C, 2, image.device, "channel_stats: pre")
+    out = torch.empty((C, 4), dtype=torch.float64, device=image.device)
+    ws = workspace(need, image.device)
+    with _Timed("channel stats %d %d" % (n, C), 0.0, 8.0 * image.numel()):
+        check(L.vnet_channel_stats(_ptr(image), _ptr(pre), _ptr(out), n, C, _ptr(ws), need, _stream()), "vnet_channel_stats")
+    return out
+
+
+def window_intensity(image, prm, out=None):
+    """transforms._window on a float32 device tensor [..., C], per channel: prm = [C, 5] rows {a, b, wmin, scale, flag}
+    (vnet_tensorflow_amd/prepare.py: window_params); v = (x - a) / b, then clip((v - wmin) * scale + 0, 0, 255), or for flag != 0
+    v < wmin ? 0 : 255, rounded to float once.  out: None = a new tensor; `image` itself = in place."""
+    n, C = _channels_last(image, "window_intensity")
+    prm = _rows(prm, C, 5, image.device, "window_intensity: prm")
+    if out is None:
+        out = torch.empty(tuple(image.shape), dtype=torch.float32, device=image.device)
+    elif out is not image:
+        if _channels_last(out, "window_intensity") != (n, C) or out.device != image.device:
+            raise VnetHipError("window_intensity: out %s for an image %s" % (tuple(out.shape), tuple(image.shape)))
+    with _Timed("window intensity %d %d" % (n, C), 0.0, 8.0 * image.numel()):
+        check(_lib.lib().vnet_window_intensity(_ptr(image), _ptr(out), _ptr(prm), n, C, _stream()), "vnet_window_intensity")
+    return out
+
+
+def crop_window(src, start, size, out=None):
+    """The window of `size` voxels at `start` of a dense device tensor, zero where it reaches past the extent (np.pad, then slice):
+    float32 [X,Y,Z,C] -> [P0,P1,P2,C] or int32 [X,Y,Z] -> [P0,P1,P2].  0 <= start < extent on every axis.  out: the caller's slot
+    (dense, any 4-byte offset: off a 16-byte boundary it takes the one-word path, with the same values), or None = a new tensor."""
+    start, size = _three(start, "crop_window: start"), _three(size, "crop_window: size")
+    _need_gpu(src, "crop_window", any_dtype=True)
+    if not ((src.dim() == 4 and src.dtype == torch.float32) or (src.dim() == 3 and src.dtype == torch.int32)):
+        raise VnetHipError("crop_window: takes float32 [X,Y,Z,C] or int32 [X,Y,Z], got %s %s" % (src.dtype, tuple(src.shape)))
+    if src.numel() == 0 or not src.is_contiguous():
+        raise VnetHipError("crop_window: the source is dense and not empty")
+    X, Y, Z = (int(v) for v in src.shape[:3])
+    C = int(src.shape[3]) if src.dim() == 4 else 1
+    if any(s < 0 or s >= n or p < 1 for s, p, n in zip(start, size, (X, Y, Z))):
+        raise ValueError("crop_window: window %s + %s on a volume %s" % (start, size, (X, Y, Z)))
+    shape = size + tuple(src.shape[3:])
+    if out is None:
+        out = torch.empty(shape, dtype=src.dtype, device=src.device)
+    elif tuple(out.shape) != shape or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
+        raise VnetHipError("crop_window: out is a dense %s tensor %s on the source's device" % (src.dtype, shape))
+    with _Timed("crop window %dx%dx%d %d" % (size + (C,)), 0.0, 8.0 * out.numel()):
+        check(_lib.lib().vnet_crop_words(_ptr(src), _ptr(out), X, Y, Z, C, *start, *size, _stream()), "vnet_crop_words")
+    return out
+
+
+def argmax_label(vol):
+    """float32 device tensor [..., K] -> int32 [...]: the first index of the largest value, a NaN larger than every number
+    (torch.argmax(vol, -1) as int32, in one pass and 4 bytes per voxel)."""
+    n, K = _channels_last(vol, "argmax_label")
+    out = torch.empty(tuple(vol.shape[:-1]), dtype=torch.int32, device=vol.device)
+    with _Timed("argmax label %d %d" % (n, K), 0.0, 4.0 * (vol.numel() + n)):
+        check(_lib.lib().vnet_argmax_label(_ptr(vol), _ptr(out), n, K, _stream()), "vnet_argmax_label")
+    return out
+
+
 # ---- stand-alone activation (API parity with layers2.prelu; the networks use the fused bn_act) ------------
 class _ActFn(torch.autograd.Function):
     @staticmethod
