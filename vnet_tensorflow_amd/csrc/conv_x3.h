@@ -18,8 +18,12 @@
 //   * the two z-planes of the brick go to two groups of four waves; the four waves of a group hold the SAME 8 output rows (32
 //     accumulator registers) and split K: wave kw owns the tap column dx = kw (12 pairs), a quarter of the column dx = 4 and
 //     one of the three pairs of the row (4,4) (16 / 16 / 15 / 16 pairs, rotated by chunk; round 5 had 65 pairs, 16 / 16 / 16 / 17, and the
-//     wave with 17 set the pace of every chunk).  So every filter fragment is fetched by exactly two waves of the workgroup,
-//     straight from L2 into VGPRs (3 KB per pair, ~16 B/clk/CU) and never touches LDS;
+//     wave with 17 set the pace of every chunk).  So every filter fragment is fetched by exactly two waves of the workgroup (one
+//     cout block per item; one wave with two, next point), straight from L2 into VGPRs (3 KB per pair, ~16 B/clk/CU), never via LDS;
+//   * items of TWO cout blocks (NB = 2, where a layer has them: conv_x3.hip) split the other way: group g takes cout block g of the
+//     pair on BOTH z-planes -- the same 64 accumulator registers (2 planes x 8 rows), one filter fragment set feeding two plane
+//     walks.  Every filter fragment is then fetched by exactly ONE wave of the workgroup (~8 B/clk/CU) and a wave waits for filter
+//     loads four times per step, not eight; LDS reads, MFMAs and every accumulator's MFMA sequence are those of the plane split;
 //   * y-sliding reuse: a wave walks the tile rows j of a (dz pair, dx) once and feeds row j to the output rows m = j - dy of
 //     every dy it owns: 12 row fragments (x3 pieces) for 40 (row, dy) steps = 240 MFMAs: 0.15 KB of LDS reads per MFMA;
 //   * the four partial bricks of a group meet in LDS (tile space, 64 KB) at the end of an item; each wave sums and stores 2 rows;
@@ -157,9 +161,13 @@ __device__ __forceinline__ void x3_yrows_single(f32x4 (&acc)[8], const unsigned 
     });
 }
 
-// NB: 16-cout blocks per item (1 or 2).  With two, a step runs the four pieces twice on the SAME tile -- once per block, one block's
-// accumulators and filter fragments at a time -- so the tile commit, its two barriers and the item's reduction are paid once per
-// 2 x 6048 MFMAs instead of once per 6048 (63 pairs x 8 rows x 6 products x 2 planes).
+// NB: 16-cout blocks per item (1 or 2).  With two, the tile commit, its two barriers and the item's reduction are paid once per
+// 2 x 6048 MFMAs instead of once per 6048 (63 pairs x 8 rows x 6 products x 2 planes), and the wave groups split the BLOCKS instead
+// of the planes: group g runs every piece of block g on plane 0 and then on plane 1 from one set of filter fragments, so a fragment
+// is loaded by one wave of the workgroup, once.  (The plane split of NB = 1 run twice -- once per block -- computed the same sums
+// with every fragment loaded by waves w and w + 4; each accumulator's MFMA order is the same in both, the results are bit-equal:
+// tests/test_hip_x3_block_split.py.)  In the epilogue the partial bricks go where the plane split would have put them, so the
+// reduction, the stores and the statistics do not know the difference.
 template <bool STATS, int NB, bool W8 = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) conv5_x3_kernel(ConvArgs a) {
     constexpr int NT = 512;
@@ -168,16 +176,18 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     static_assert(XT::PER * XT::RPI == XT::ROWS && XT::PER == X3G<false>::SPER, "every staging pass covers whole tile rows");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* tile = smem;
-    float* red = reinterpret_cast<float*>(smem);                              // after an item's K loop: [8 waves][NB][8 rows][64 lanes][4]
+    float* red = reinterpret_cast<float*>(smem);                              // after an item's K loop: [plane][kw][NB][8 rows][64 lanes][4]
     float* sred = reinterpret_cast<float*>(smem + G::TILEB);                  // [8 waves][2 x 16] epilogue statistics
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, g = lane >> 4, half = g & 1, hi = g >> 1;
     const int grp = wave >> 2, kw = wave & 3;
 
-    // (narrow brick: lanes 8..15 of a column block are the plane two further)
+    // (narrow brick: lanes 8..15 of a column block are the plane two further; NB = 2: the wave walks both planes, the plane is a
+    //  compile-time offset in the K loop)
+    static_assert(NB == 1 || !W8, "the block split is built for the wide brick");
     const int base0 = W8 ? half * G::PLANEB + (grp + 2 * (j >> 3)) * G::ZB + (j & 7) * 16
-                         : half * G::PLANEB + ((grp * G::IY) * G::IX + j) * 16;
+                         : half * G::PLANEB + (((NB == 2 ? 0 : grp) * G::IY) * G::IX + j) * 16;
     const unsigned char* bZ = tile + base0 + hi * G::ZB;                      // taps (dz, dz + 1)
     const unsigned char* bY = tile + base0 + hi * G::ROWB + 4 * G::ZB;        // taps (4, dy), (4, dy + 1)
     const unsigned char* b0 = tile + base0 + 4 * G::ZB;                       // tap (4, 4, dx) alone
@@ -321,36 +331,46 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
         // together, and because the halves are then half a pass apart, the L2 round trip of a piece's filter fragments (loaded at the
         // piece's head, into ONE register set) hides under the other half's MFMAs: a prefetch one piece ahead (a second set of 60
         // registers) measured the same (profiles/r05_x3_experiments.txt) and is what kept two cout blocks per item from fitting.
-        x3_for<NB>([&](auto NBI) {
-            constexpr int nb = decltype(NBI)::value;
-            const unsigned wc = (unsigned)(ch * X3_NPAIR * ncob + cob + nb) * 3u * 64u;      // pair 0 of (chunk, cout block), in 16-byte units
+        {
+            // NB = 1: this wave's plane (in base0), the item's block.  NB = 2: cout block `grp` of the pair, BOTH planes -- every piece
+            // runs on plane 0 and then on plane 1 from the same filter registers (acc[p]: plane p; + p * ZB on the lane base)
+            const unsigned wc = (unsigned)(ch * X3_NPAIR * ncob + cob + (NB == 2 ? grp : 0)) * 3u * 64u;      // pair 0 of (chunk, cout block), in 16-byte units
             bf16x8 A[5][3];
             if (grp) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
             x3_load_a<5>(A, wbase, wc + (unsigned)(kc * 5) * astride, astride, lane);               // (dz 0|1, dx = kc)
             __builtin_amdgcn_sched_barrier(0);
-            x3_zrows<G, 0, 5>(acc[nb], bZ + kc * 16, A);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (nb == 0) VNET_STAMP(1);
+            x3_for<NB>([&](auto PI) {
+                constexpr int p = decltype(PI)::value, po = p * G::ZB;
+                x3_zrows<G, 0, 5>(acc[p], bZ + po + kc * 16, A);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            VNET_STAMP(1);
             x3_load_a<5>(A, wbase, wc + (unsigned)(25 + kc * 5) * astride, astride, lane);          // (dz 2|3, dx = kc)
             __builtin_amdgcn_sched_barrier(0);
-            x3_zrows<G, 0, 5>(acc[nb], bZ + 2 * G::ZB + kc * 16, A);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (nb == 0) VNET_STAMP(2);
+            x3_for<NB>([&](auto PI) {
+                constexpr int p = decltype(PI)::value, po = p * G::ZB;
+                x3_zrows<G, 0, 5>(acc[p], bZ + po + 2 * G::ZB + kc * 16, A);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            VNET_STAMP(2);
             x3_load_a1(A[0], wbase, wc + (unsigned)(50 + kc * 2) * astride, lane);                  // (dz 4, dy 0|1, dx = kc)
             x3_load_a1(A[1], wbase, wc + (unsigned)(51 + kc * 2) * astride, lane);                  // (dz 4, dy 2|3, dx = kc)
             x3_load_a1(A[2], wbase, wc + (unsigned)(60 + (kc & 1)) * astride, lane);                // taps (4, 4, 0|1) with kc == 0, (4, 4, 2|3) with kc == 1
             x3_load_a1(A[3], wbase, wc + 62u * astride, lane);                                     // tap (4, 4, 4): goes with kc == 3
             __builtin_amdgcn_sched_barrier(0);
             if (grp) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1);
-            // the next tile's loads go out in the LAST pass, behind this piece's filter loads (vmcnt counts in order) and late enough
+            // the next tile's loads go out once per step, behind the third piece's filter loads (vmcnt counts in order) and late enough
             // that its 48 registers are live for two pieces only; unconditional: a branch around an issue merges two vmcnt states
-            if constexpr (nb == NB - 1) tile_issue(min(step + 1, nsteps - 1));
+            tile_issue(min(step + 1, nsteps - 1));
             __builtin_amdgcn_sched_barrier(0);
-            x3_yrows_pairs<G, 0, 5>(acc[nb], bY + kc * 16, A);
-            if (kc < 2) x3_yrows_single<G, 2, 5>(acc[nb], bX + kc * 32, A);          // columns (0|1) / (2|3) of row (4, 4)
-            if (kc == 3) x3_yrows_single<G, 3, 5>(acc[nb], b0 + 4 * 16, A);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (nb == 0) VNET_STAMP(3);
+            x3_for<NB>([&](auto PI) {
+                constexpr int p = decltype(PI)::value, po = p * G::ZB;
+                x3_yrows_pairs<G, 0, 5>(acc[p], bY + po + kc * 16, A);
+                if (kc < 2) x3_yrows_single<G, 2, 5>(acc[p], bX + po + kc * 32, A);      // columns (0|1) / (2|3) of row (4, 4)
+                if (kc == 3) x3_yrows_single<G, 3, 5>(acc[p], b0 + po + 4 * 16, A);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            VNET_STAMP(3);
             // the column dx = 4 in four parts (3 / 3 / 3 / 3 + 1 pairs): pairs 20-22 | 23, 24, 45 | 46-48 | 49, 58, 59 (+ 62 above)
             {
                 const int p0 = kc == 0 ? 20 : kc == 1 ? 23 : kc == 2 ? 46 : 49;
@@ -361,29 +381,34 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
                 x3_load_a1(A[2], wbase, wc + (unsigned)p2 * astride, lane);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (kc == 0) {
-                x3_zrows<G, 0, 3, 0, 5>(acc[nb], bZ + 4 * 16, A);
-            } else if (kc == 1) {
-                x3_zrows<G, 3, 2, 0, 5>(acc[nb], bZ + 4 * 16, A);
-                x3_zrows<G, 0, 1, 2, 5>(acc[nb], bZ + 2 * G::ZB + 4 * 16, A);
-            } else if (kc == 2) {
-                x3_zrows<G, 1, 3, 0, 5>(acc[nb], bZ + 2 * G::ZB + 4 * 16, A);
-            } else {
-                x3_zrows<G, 4, 1, 0, 5>(acc[nb], bZ + 2 * G::ZB + 4 * 16, A);
-                x3_yrows_pairs<G, 1, 5>(acc[nb], bY + 4 * 16, A);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        });
+            x3_for<NB>([&](auto PI) {
+                constexpr int p = decltype(PI)::value, po = p * G::ZB;
+                if (kc == 0) {
+                    x3_zrows<G, 0, 3, 0, 5>(acc[p], bZ + po + 4 * 16, A);
+                } else if (kc == 1) {
+                    x3_zrows<G, 3, 2, 0, 5>(acc[p], bZ + po + 4 * 16, A);
+                    x3_zrows<G, 0, 1, 2, 5>(acc[p], bZ + po + 2 * G::ZB + 4 * 16, A);
+                } else if (kc == 2) {
+                    x3_zrows<G, 1, 3, 0, 5>(acc[p], bZ + po + 2 * G::ZB + 4 * 16, A);
+                } else {
+                    x3_zrows<G, 4, 1, 0, 5>(acc[p], bZ + po + 2 * G::ZB + 4 * 16, A);
+                    x3_yrows_pairs<G, 1, 5>(acc[p], bY + po + 4 * 16, A);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        }
         VNET_STAMP(4);
         __builtin_amdgcn_s_setprio(0);
         __syncthreads();                                   // every wave is done reading the tile
         VNET_STAMP(5);
         if (last) {
-            // the four partial bricks of each group meet in LDS; wave kw sums and stores the output rows 2 kw, 2 kw + 1
+            // the four partial bricks of each (plane, block) meet in LDS; wave (grp, kw) sums and stores the output rows 2 kw, 2 kw + 1 of plane grp
             const bool flip = lc & 1;                      // the item's last chunk ran negated
+            // (NB = 2: acc[nb] is PLANE nb of cout block grp -- it goes where wave (nb, kw) of the plane split would have put its block grp)
             x3_for<8 * NB>([&](auto MI) {
                 constexpr int nb = decltype(MI)::value / 8, m = decltype(MI)::value % 8;
-                *reinterpret_cast<f32x4*>(red + (((wave * NB + nb) * 8 + m) * 64 + lane) * 4) = flip ? -acc[nb][m] : acc[nb][m];
+                const int slot = NB == 2 ? (nb * 4 + kw) * NB + grp : wave;
+                *reinterpret_cast<f32x4*>(red + ((slot * 8 + m) * 64 + lane) * 4) = flip ? -acc[nb][m] : acc[nb][m];
             });
             __syncthreads();
             x3_for<NB>([&](auto NBI) {
