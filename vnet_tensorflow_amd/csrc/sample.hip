@@ -1,14 +1,8 @@
 // sample.hip -- the random tail of the training pipeline on device-resident prepared cases (include/vnet_hip_sample.h; reference
 // NiftiDataset3D.py: ConfidenceCrop2 661-793, RandomCrop 458-551, RandomFlip 187-208, RandomNoise 553-572), gfx950.
 //   vnet_cc_table     : the representative map of components.hip -> dense rows {representative, count, lo[3], hi[3]} in ascending
-//                       representative order.  The rank of a root (the number of roots with a smaller index) is a device-wide prefix sum,
-//                       written as three launches so that NO thread waits for another (no look-back, no flags, no spin):
-//                         count : every block counts the roots of its own contiguous chunk of voxels
-//                         scan  : one block turns the block counts into exclusive offsets, writes n and zeroes the rows past it
-//                         rank  : every block walks its chunk in order and ranks its roots with ballots; a root writes its row's head
-//                                 and leaves its rank where its count stood (the count array becomes the root -> row map)
-//                       and a fourth pass folds every voxel's coordinates into its row with atomicMin / atomicMax, combined per wave
-//                       first (components.hip's counting scheme: a solid organ issues one set of atomics per wave-trip run, not per voxel).
+//                       representative order: the count / scan / rank / box launches of cc_table.h (shared with score.hip, which adds
+//                       the index sums to the box pass), here without the sums.
 //   vnet_window_count : grid-stride over a window, wave reduction, one 64-bit atomicAdd pair per wave.
 //   vnet_sample_patch : one kernel writes image and label of one sample: gather with per-axis reversal, Philox4x32-10 + Box-Muller noise
 //                       keyed by (seed, output element).  Channel quads with 16-byte accesses or one channel (resample.hip's rule),
@@ -17,176 +11,11 @@
 #include <math.h>
 #include <limits.h>
 #include "common.h"
+#include "cc_table.h"
 #include "../../include/vnet_hip_components.h"
 #include "../../include/vnet_hip_sample.h"
 
 namespace {
-
-constexpr int SP_BLOCK = 256, SP_MAXBLK = 4096, SP_WAVES = SP_BLOCK / 64;
-
-typedef unsigned long long u64;
-
-inline int sp_blocks(size_t units) {
-    size_t b = (units + SP_BLOCK - 1) / SP_BLOCK;
-    return (int)(b < 1 ? 1 : b > SP_MAXBLK ? SP_MAXBLK : b);
-}
-
-// 0 and the voxel count, VNET_E_BADARG on a size < 1, VNET_E_UNSUPPORTED when an int32 cannot index the volume
-inline int sp_count(int X, int Y, int Z, size_t& n) {
-    if (X < 1 || Y < 1 || Z < 1) return VNET_E_BADARG;
-    n = (size_t)X * (size_t)Y * (size_t)Z;
-    return n > (size_t)INT_MAX ? VNET_E_UNSUPPORTED : 0;
-}
-
-// ---- component table ------------------------------------------------------------------------------------------------------------
-// Chunks: block b owns voxels [b * chunk, min(n, (b + 1) * chunk)), chunk a multiple of SP_BLOCK, at most SP_MAXBLK blocks.
-struct TableP {
-    const int* roots;      // representative map (vnet_cc_roots)
-    int* sizes;            // count at the representative; after the rank pass: the representative's row, -1 past the capacity
-    int* blk;              // [SP_MAXBLK] root count of each block, then its exclusive offset
-    int* n;
-    int* table;
-    int cap, nblk;
-    size_t nvox, chunk;
-    int Y, Z;
-};
-
-__global__ void __launch_bounds__(SP_BLOCK) table_count_kernel(TableP p) {
-    __shared__ int wsum[SP_WAVES];
-    const size_t lo = (size_t)blockIdx.x * p.chunk, hi = lo + p.chunk < p.nvox ? lo + p.chunk : p.nvox;
-    int c = 0;
-    for (size_t idx = lo + threadIdx.x; idx < hi; idx += SP_BLOCK) c += p.roots[idx] == (int)idx;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-#pragma unroll
-        for (int w = 0; w < SP_WAVES; ++w) s += wsum[w];
-        p.blk[blockIdx.x] = s;
-    }
-}
-
-// one block: blk[b] <- sum of blk[0 .. b), *n <- the total, rows [min(n, cap), cap) <- 0
-__global__ void __launch_bounds__(SP_BLOCK) table_scan_kernel(TableP p) {
-    constexpr int PER = SP_MAXBLK / SP_BLOCK;
-    __shared__ int part[SP_BLOCK];
-    __shared__ int total;
-    int v[PER], s = 0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int b = threadIdx.x * PER + i;
-        v[i] = b < p.nblk ? p.blk[b] : 0;
-        s += v[i];
-    }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {                          // 256 adds by one thread, once per case
-        int run = 0;
-        for (int t = 0; t < SP_BLOCK; ++t) { const int c = part[t]; part[t] = run; run += c; }
-        total = run;
-        *p.n = run;
-    }
-    __syncthreads();
-    int run = part[threadIdx.x];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int b = threadIdx.x * PER + i;
-        if (b < p.nblk) p.blk[b] = run;
-        run += v[i];
-    }
-    const int first = total < p.cap ? total : p.cap;
-    for (int w = first * VNET_CC_ROW + threadIdx.x; w < p.cap * VNET_CC_ROW; w += SP_BLOCK) p.table[w] = 0;
-}
-
-// The loop runs on the block's base index so that all lanes of a wave make every trip together (wave-wide votes).
-__global__ void __launch_bounds__(SP_BLOCK) table_rank_kernel(TableP p) {
-    __shared__ int wcnt[2][SP_WAVES];                // double-buffered by trip parity: one barrier per trip
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t lo = (size_t)blockIdx.x * p.chunk, hi = lo + p.chunk < p.nvox ? lo + p.chunk : p.nvox;
-    int run = p.blk[blockIdx.x];                     // roots in front of this trip
-    int trip = 0;
-    for (size_t base = lo; base < hi; base += SP_BLOCK, trip ^= 1) {
-        const size_t idx = base + threadIdx.x;
-        const bool root = idx < hi && p.roots[idx] == (int)idx;
-        const u64 m = __ballot(root);
-        if (lane == 0) wcnt[trip][wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < SP_WAVES; ++w) {
-            const int c = wcnt[trip][w];
-            before += w < wave ? c : 0;
-            all += c;
-        }
-        if (root) {
-            const int k = run + before + __popcll(m & ((1ull << lane) - 1ull));
-            const int count = p.sizes[idx];
-            p.sizes[idx] = k < p.cap ? k : -1;
-            if (k < p.cap) {
-                int* row = p.table + (size_t)k * VNET_CC_ROW;
-                row[0] = (int)idx; row[1] = count;
-                row[2] = INT_MAX; row[3] = INT_MAX; row[4] = INT_MAX;
-                row[5] = 0; row[6] = 0; row[7] = 0;
-            }
-        }
-        run += all;
-    }
-}
-
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
-    return v;
-}
-
-__device__ __forceinline__ void box_fold(int* row, const int lo[3], const int hi[3]) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { atomicMin(row + 2 + a, lo[a]); atomicMax(row + 5 + a, hi[a]); }
-}
-
-// The lanes that share the first foreground lane's root fold their extremes once per run of trips with that root; the others one each.
-__global__ void __launch_bounds__(SP_BLOCK) table_box_kernel(TableP p) {
-    const int lane = threadIdx.x & 63;
-    int acc_row = -1, alo[3] = {INT_MAX, INT_MAX, INT_MAX}, ahi[3] = {0, 0, 0};      // wave-uniform
-    int acc_root = -1;
-    for (size_t base = (size_t)blockIdx.x * SP_BLOCK; base < p.nvox; base += (size_t)gridDim.x * SP_BLOCK) {
-        const size_t idx = base + threadIdx.x;
-        const int r = idx < p.nvox ? p.roots[idx] : -1;
-        const bool fg = r >= 0;
-        const u64 m = __ballot(fg);
-        if (m == 0) continue;
-        const unsigned row_i = (unsigned)idx / (unsigned)p.Z;
-        int c[3];
-        c[2] = (int)((unsigned)idx - row_i * (unsigned)p.Z); c[1] = (int)(row_i % (unsigned)p.Y); c[0] = (int)(row_i / (unsigned)p.Y);
-        const int r0 = __shfl(r, __ffsll(m) - 1, 64);
-        const bool same = fg && r == r0;
-        if (r0 != acc_root) {
-            if (acc_row >= 0 && lane == 0) box_fold(p.table + (size_t)acc_row * VNET_CC_ROW, alo, ahi);
-            acc_root = r0;
-            acc_row = p.sizes[r0];                   // (-1: a component past the capacity has no row)
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { alo[a] = INT_MAX; ahi[a] = 0; }
-        }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const int l = wave_min_i(same ? c[a] : INT_MAX), h = wave_max_i(same ? c[a] : 0);
-            alo[a] = l < alo[a] ? l : alo[a];
-            ahi[a] = h > ahi[a] ? h : ahi[a];
-        }
-        if (fg && !same) {
-            const int k = p.sizes[r];
-            if (k >= 0) box_fold(p.table + (size_t)k * VNET_CC_ROW, c, c);
-        }
-    }
-    if (acc_row >= 0 && lane == 0) box_fold(p.table + (size_t)acc_row * VNET_CC_ROW, alo, ahi);
-}
 
 // ---- window count ---------------------------------------------------------------------------------------------------------------
 __global__ void window_zero_kernel(u64* out) {
@@ -295,28 +124,11 @@ extern "C" {
 
 size_t vnet_cc_table_ws_bytes(int X, int Y, int Z) {
     size_t n = 0;
-    return sp_count(X, Y, Z, n) ? 0 : 8 * n + sizeof(int) * SP_MAXBLK;
+    return sp_count(X, Y, Z, n) ? 0 : cc_table_bytes(n);
 }
 
 int vnet_cc_table(const int* label, int* n_out, int* table, int max_components, int X, int Y, int Z, void* ws, size_t ws_bytes, void* stream) {
-    size_t n = 0;
-    if (!label || !n_out || !table || !ws || (reinterpret_cast<uintptr_t>(ws) & 7) || max_components < 1) return VNET_E_BADARG;
-    if (int e = sp_count(X, Y, Z, n)) return e;
-    if ((size_t)max_components > (size_t)INT_MAX / VNET_CC_ROW) return VNET_E_UNSUPPORTED;
-    if (ws_bytes < 8 * n + sizeof(int) * SP_MAXBLK) return VNET_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    TableP p{};
-    p.blk = static_cast<int*>(ws);                   // (in front: the voxel arrays behind it stay 8-byte aligned whatever n is)
-    int* roots = p.blk + SP_MAXBLK;
-    p.roots = roots; p.sizes = roots + n; p.n = n_out; p.table = table; p.cap = max_components;
-    p.nvox = n; p.Y = Y; p.Z = Z;
-    p.chunk = align_up((n + SP_MAXBLK - 1) / SP_MAXBLK, (size_t)SP_BLOCK);
-    p.nblk = (int)((n + p.chunk - 1) / p.chunk);
-    if (int e = vnet_cc_roots(label, roots, p.sizes, X, Y, Z, stream)) return e;
-    if (int e = launch<table_count_kernel>(dim3(p.nblk), dim3(SP_BLOCK), 0, st, p)) return e;
-    if (int e = launch<table_scan_kernel>(dim3(1), dim3(SP_BLOCK), 0, st, p)) return e;
-    if (int e = launch<table_rank_kernel>(dim3(p.nblk), dim3(SP_BLOCK), 0, st, p)) return e;
-    return launch<table_box_kernel>(dim3(sp_blocks(n)), dim3(SP_BLOCK), 0, st, p);
+    return cc_table_run<false>(label, n_out, table, nullptr, max_components, X, Y, Z, ws, ws_bytes, stream);
 }
 
 int vnet_window_count(const int* label, long long* out, int X, int Y, int Z, int sx, int sy, int sz, int wx, int wy, int wz,

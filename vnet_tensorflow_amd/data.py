@@ -3,7 +3,7 @@
 [X,Y,Z,Cin] (axis order after the (2,1,0) transpose, NiftiDataset3D.py:154), label int32
 [X,Y,Z] remapped to class *indices* of SegmentationClasses (NiftiDataset3D.py:125-137).
 
-Sources: a case directory tree holding `.npy` or uncompressed NIfTI-1 `.nii` files, or the
+Sources: a case directory tree holding `.npy` or single-file NIfTI-1 `.nii` / `.nii.gz` files, or the
 synthetic generator of SURVEY.md 8(d) (the shipped sample volumes are Git-LFS stubs).  Without a
 transform list the pure index-math RandomCrop to PatchShape is applied; with one (transforms.py),
 the case's voxel spacing travels with the sample, which is what `Resample` reads."""
@@ -13,26 +13,51 @@ import struct
 import numpy as np
 
 
-# ---- minimal NIfTI-1 (single-file, uncompressed) ------------------------------------------------
+# ---- minimal NIfTI-1 (single-file; written uncompressed, read also gzip-compressed) ------------------------------------------------
 _NIFTI_DTYPES = {2: np.uint8, 4: np.int16, 8: np.int32, 16: np.float32, 64: np.float64, 256: np.int8,
                  512: np.uint16, 768: np.uint32}
 
 
-def read_nifti(path):
-    """Returns (array [X,Y,Z], header dict).  NIfTI stores x fastest, i.e. Fortran order [X,Y,Z]."""
-    with open(path, "rb") as f:
+def _open_nifti(path):
+    """The file object of a single-file NIfTI-1: gzip-compressed for `.nii.gz` (standard library), plain otherwise."""
+    if path.endswith(".gz"):
+        import gzip
+        return gzip.open(path, "rb")
+    return open(path, "rb")
+
+
+def _nifti_header(f, path):
+    """The 348 header bytes of an open file.  A compressed file is decompressed only as far as they reach."""
+    try:
         hdr = f.read(348)
-        if len(hdr) < 348 or struct.unpack("<i", hdr[:4])[0] != 348:
-            raise ValueError("%s: not a little-endian NIfTI-1 file (Git-LFS pointer?)" % path)
+    except (EOFError, OSError) as e:                 # a truncated or damaged gzip stream (gzip.BadGzipFile is an OSError)
+        raise ValueError("%s: not a readable NIfTI-1 file (%s)" % (path, e))
+    if len(hdr) < 348 or struct.unpack("<i", hdr[:4])[0] != 348:
+        raise ValueError("%s: not a little-endian NIfTI-1 file (Git-LFS pointer?)" % path)
+    return hdr
+
+
+def read_nifti(path):
+    """Returns (array [X,Y,Z], header dict).  NIfTI stores x fastest, i.e. Fortran order [X,Y,Z].  `.nii` or gzip-compressed
+    `.nii.gz`."""
+    with _open_nifti(path) as f:
+        hdr = _nifti_header(f, path)
         dim = struct.unpack("<8h", hdr[40:56])
         datatype, bitpix = struct.unpack("<hh", hdr[70:74])
         pixdim = struct.unpack("<8f", hdr[76:108])
         vox_offset = struct.unpack("<f", hdr[108:112])[0]
         slope, inter = struct.unpack("<ff", hdr[112:120])
         shape = tuple(int(d) for d in dim[1:1 + dim[0]])
-        f.seek(int(vox_offset))
         dt = _NIFTI_DTYPES[datatype]
-        data = np.frombuffer(f.read(int(np.prod(shape)) * np.dtype(dt).itemsize), dtype=dt).reshape(shape, order="F")
+        nbytes = int(np.prod(shape)) * np.dtype(dt).itemsize
+        try:
+            f.seek(int(vox_offset))
+            raw = f.read(nbytes)
+        except (EOFError, OSError) as e:
+            raise ValueError("%s: the voxel array cannot be read (%s)" % (path, e))
+        if len(raw) < nbytes:
+            raise ValueError("%s: truncated, %d of %d bytes of the voxel array" % (path, len(raw), nbytes))
+        data = np.frombuffer(raw, dtype=dt).reshape(shape, order="F")
     if slope not in (0.0, 1.0) or inter != 0.0:
         data = data.astype(np.float32) * (slope if slope != 0 else 1.0) + inter
     return data, {"pixdim": pixdim[1:4], "dim": shape, "datatype": datatype}
@@ -56,13 +81,11 @@ def write_nifti(path, arr, pixdim=(1.0, 1.0, 1.0)):
 
 
 def volume_spacing(path):
-    """Voxel spacing (pixdim) of a volume file -- from the 348-byte NIfTI-1 header alone, the voxel array is not read;
-    (1, 1, 1) for .npy arrays, which carry none."""
-    if path.endswith(".nii"):
-        with open(path, "rb") as f:
-            hdr = f.read(348)
-        if len(hdr) < 348 or struct.unpack("<i", hdr[:4])[0] != 348:
-            raise ValueError("%s: not a little-endian NIfTI-1 file (Git-LFS pointer?)" % path)
+    """Voxel spacing (pixdim) of a volume file -- from the 348-byte NIfTI-1 header alone, the voxel array is not read (of a `.nii.gz`
+    only the header's bytes are decompressed); (1, 1, 1) for .npy arrays, which carry none."""
+    if path.endswith((".nii", ".nii.gz")):
+        with _open_nifti(path) as f:
+            hdr = _nifti_header(f, path)
         return tuple(float(v) for v in struct.unpack("<8f", hdr[76:108])[1:4])
     return (1.0, 1.0, 1.0)
 
@@ -70,9 +93,9 @@ def volume_spacing(path):
 def load_volume(path):
     if path.endswith(".npy"):
         return np.load(path)
-    if path.endswith(".nii"):
+    if path.endswith((".nii", ".nii.gz")):
         return read_nifti(path)[0]
-    raise ValueError("unsupported volume format: %s (.npy or uncompressed .nii; SimpleITK is not available)" % path)
+    raise ValueError("unsupported volume format: %s (.npy, .nii or .nii.gz single-file NIfTI-1; SimpleITK is not available)" % path)
 
 
 def remap_labels(label, classes):

@@ -962,7 +962,7 @@ class image2label(object):
     # -- reference model.py:817-977 (array in / arrays out) ----------------------------------------------------------
     @in_context
     def evaluate_single_3D(self, images_np, back_size=None, back_ratio=None, largest_component=False, volume_threshold=None,
-                           spacing=None, extent=None):
+                           spacing=None, extent=None, on_label=None):
         """images_np float32 [X,Y,Z,Cin] -> (label int64 [X,Y,Z], softmax float32 [K,X,Y,Z]).
         Patch enumeration, the duplicated last batch and argmax-of-summed-softmax follow
         model.py:866-937 exactly; accumulation runs on the GPU.
@@ -977,7 +977,10 @@ class image2label(object):
         images_np may also be a float32 tensor [X,Y,Z,Cin] on the model's device (a case prepared there, prepare.prepare_on_device):
         the same windows in the same batches, each cut on the device by ops.crop_window into its slot of the batch -- no worker
         threads, no pinned staging, no prepare_batch -- and the label formed by ops.argmax_label.  The results are NumPy arrays with
-        the values of the array path."""
+        the values of the array path.
+        on_label: a callable that receives the label as an int32 tensor on the device, on the grid and with the values it is returned
+        with -- after the way back and the label filters, before the copy to the host (batch_evaluate scores it there).  What the
+        function returns does not depend on it; None: nothing is formed for it."""
         vt = volume_threshold if volume_threshold is not None and volume_threshold > 0 else None
         filtered = bool(largest_component) or vt is not None
         sp = tuple(float(v) for v in spacing) if spacing is not None else (1.0, 1.0, 1.0)
@@ -986,6 +989,10 @@ class image2label(object):
             if largest_component:
                 return ops.largest_component(label, classes=self.output_channel_num, min_volume=vt, spacing=sp)
             return ops.volume_threshold(label, vt, sp)
+        def seen(label):
+            if on_label is not None:
+                on_label(label if label.dtype == torch.int32 else label.to(torch.int32))
+            return label
         ps, st = list(self.patch_shape), list(self.evaluate_stride)
         pads = [(0, max(p - s, 0)) for s, p in zip(images_np.shape[:3], ps)]
         orig = tuple(int(v) for v in images_np.shape[:3])
@@ -1040,7 +1047,7 @@ class image2label(object):
                 sm = self._infer(batch)
                 for j, idx in enumerate(bd['indexes']):
                     ops.accumulate_patch(sm[j], vol, cnt, (idx[0], idx[2], idx[4]))
-            return self._device_case_results(vol, cnt, orig, back_size, back_ratio, filters if filtered else None, extent)
+            return self._device_case_results(vol, cnt, orig, back_size, back_ratio, filters if filtered else None, extent, seen)
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=int(getattr(self, "loader_threads", 3))) as pool:
             def windowed(depth=3):
@@ -1063,7 +1070,7 @@ class image2label(object):
             label = ops.resample(torch.argmax(vol, dim=-1).to(torch.int32), back_size, back_ratio, "nearest")
             if filtered:
                 label = filters(label)
-            label_np = label.cpu().numpy().astype(np.int64)
+            label_np = seen(label).cpu().numpy().astype(np.int64)
             if not self.evaluate_probability_output:
                 return label_np, None
             prob = ops.resample(vol, back_size, back_ratio, "linear", divisor=cnt)
@@ -1073,11 +1080,13 @@ class image2label(object):
         if filtered:
             # the filters must see the cropped volume, not the window padding: crop on the device, filter, copy the 0/1 map out
             fl = tuple(slice(0, min(s, e)) for s, e in zip(orig, extent if extent is not None else orig))
-            label_np = filters(torch.argmax(vol, dim=-1)[fl].to(torch.int32)).cpu().numpy().astype(np.int64)
+            label_np = seen(filters(torch.argmax(vol, dim=-1)[fl].to(torch.int32))).cpu().numpy().astype(np.int64)
             if not self.evaluate_probability_output:
                 return label_np, None
             vol_np, cnt_np = vol.cpu().numpy(), cnt.cpu().numpy()
             return label_np, (np.moveaxis(vol_np, -1, 0) / np.float32(cnt_np))[(slice(None),) + sl]
+        if on_label is not None:
+            on_label(torch.argmax(vol, dim=-1)[sl].to(torch.int32).contiguous())          # (the volume the caller gets: cropped to `orig`)
         label_np = torch.argmax(vol, dim=-1).to(torch.int16 if K < 32768 else torch.int64).cpu().numpy().astype(np.int64)
         if not self.evaluate_probability_output:
             return label_np[sl], None
@@ -1085,17 +1094,18 @@ class image2label(object):
         softmax_np = np.moveaxis(vol_np, -1, 0) / np.float32(cnt_np)          # model.py:935-937
         return label_np[sl], softmax_np[(slice(None),) + sl]
 
-    def _device_case_results(self, vol, cnt, orig, back_size, back_ratio, filters, extent):
+    def _device_case_results(self, vol, cnt, orig, back_size, back_ratio, filters, extent, seen=lambda label: label):
         """What evaluate_single_3D returns for a case that lives in device memory, from the summed softmax `vol` and the count map
         `cnt`: the same values as the array path's tail above.  The label is formed by ops.argmax_label as int32 (no int64 volume,
-        no cast pass), cropped on the device, and comes down once."""
+        no cast pass), cropped on the device, and comes down once.  seen: evaluate_single_3D's on_label hook, handed the label that
+        is about to come down."""
         label = ops.argmax_label(vol)
         sl = tuple(slice(0, s) for s in orig)
         if back_size is not None:
             label = ops.resample(label, back_size, back_ratio, "nearest")
             if filters is not None:
                 label = filters(label)
-            label_np = label.cpu().numpy().astype(np.int64)
+            label_np = seen(label).cpu().numpy().astype(np.int64)
             if not self.evaluate_probability_output:
                 return label_np, None
             prob = ops.resample(vol, back_size, back_ratio, "linear", divisor=cnt)
@@ -1106,11 +1116,72 @@ class image2label(object):
             label = ops.crop_window(label, (0, 0, 0), keep)
         if filters is not None:
             label = filters(label)
-        label_np = label.cpu().numpy().astype(np.int64)
+        label_np = seen(label).cpu().numpy().astype(np.int64)
         if not self.evaluate_probability_output:
             return label_np, None
         vol_np, cnt_np = vol.cpu().numpy(), cnt.cpu().numpy()
         return label_np, (np.moveaxis(vol_np, -1, 0) / np.float32(cnt_np))[(slice(None),) + sl]
+
+    def evaluate_pipeline_transforms(self):
+        """(transform list | None, whether it changes the grid) of EvaluationSetting.Pipeline: the 'evaluate' transform list of the
+        reference's YAML (model.py:1142-1167).  Resample runs on the device here (this is the main thread and no stream capture is
+        active); the other physical-grid transforms are refused."""
+        tf, regrid = None, False
+        if self.evaluate_pipeline:
+            from . import transforms as vtf
+            tf = vtf.build_pipeline(self.evaluate_pipeline, "evaluate", geometry=True)
+            for t in tf:
+                if isinstance(t, vtf.Resample):
+                    t.device, regrid = self.device, True
+        return tf, regrid
+
+    @in_context
+    def evaluate_case(self, image, spacing, tf, regrid, on_label=None):
+        """One case of evaluate(): image float32 [X,Y,Z,Cin] of the input file with voxel size `spacing`, through the pipeline
+        (tf, regrid: evaluate_pipeline_transforms), the windows, the way back and the label filters of EvaluationSetting -> (label
+        int64, softmax | None), both on the input file's grid.  on_label: evaluate_single_3D's hook."""
+        from . import resample as vrs
+        from . import transforms as vtf
+        size = tuple(int(v) for v in image.shape[:3])
+        vt = self.evaluate_volume_threshold if self.evaluate_volume_threshold and self.evaluate_volume_threshold > 0 else None
+        on_device = {}
+        if self.evaluate_lcc or vt is not None:
+            on_device = dict(largest_component=bool(self.evaluate_lcc), volume_threshold=vt, spacing=spacing, extent=size)
+        if on_label is not None:
+            on_device["on_label"] = on_label
+        prepared = None
+        if tf is not None and self.prepare_on_device and self.device.type == "cuda":
+            # EvaluationSetting.PrepareOnDevice: the file goes up once, the pipeline and the window crops run there (None: the
+            # pipeline holds a transform the device path does not serve, and the host path below is kept)
+            from . import prepare as vprep
+            prepared = vprep.prepare_on_device(tf, torch.from_numpy(image).to(self.device), spacing)
+        if prepared is not None:
+            case, _, case_spacing = prepared
+        elif regrid:
+            sample = vtf.run_pipeline(tf, {'image': image, 'label': np.zeros(image.shape[:3], dtype=np.int32), 'spacing': spacing},
+                                      np.random.default_rng(0))
+            case, case_spacing = sample['image'], sample['spacing']
+        else:
+            case = image
+            if tf is not None:
+                case, _ = vtf.apply_pipeline(tf, image, np.zeros(image.shape[:3], dtype=np.int32), np.random.default_rng(0))
+        if regrid:
+            # the pipeline changes the grid: window on the transformed grid, then back to the input file's size and spacing
+            # (model.py:939-975) before the label filters, which work in the input's physical units
+            return self.evaluate_single_3D(case, back_size=size, back_ratio=vrs.ratios(case_spacing, spacing), **on_device)
+        label, softmax = self.evaluate_single_3D(case, **on_device)
+        label = label[tuple(slice(0, n) for n in size)]
+        if softmax is not None:
+            softmax = softmax[(slice(None),) + tuple(slice(0, n) for n in size)]
+        return label, softmax
+
+    @staticmethod
+    def write_label(out, label, spacing):
+        """The label file of evaluate(): int16, `.npy` or NIfTI-1 (a `.nii.gz` name is written uncompressed, as `.nii`)."""
+        if out.endswith(".npy"):
+            np.save(out, label.astype(np.int16))
+        else:
+            vdata.write_nifti(out[:-3] if out.endswith(".gz") else out, label.astype(np.int16), spacing)
 
     # -- reference model.py:1131-1242 ------------------------------------------------------------------------------
     @in_context
@@ -1120,17 +1191,7 @@ class image2label(object):
         self.build_model_graph()
         self._print("{}: Restoring checkpoint {}".format(_now(), self.checkpoint_path))
         self.load_checkpoint(self.checkpoint_path, with_optimizer=False)
-        tf, regrid = None, False
-        if self.evaluate_pipeline:
-            # EvaluationSetting.Pipeline: the 'evaluate' transform list of the reference's YAML (model.py:1142-1167).  Resample
-            # runs on the device here (this is the main thread and no stream capture is active); the other physical-grid
-            # transforms are refused
-            from . import resample as vrs
-            from . import transforms as vtf
-            tf = vtf.build_pipeline(self.evaluate_pipeline, "evaluate", geometry=True)
-            for t in tf:
-                if isinstance(t, vtf.Resample):
-                    t.device, regrid = self.device, True
+        tf, regrid = self.evaluate_pipeline_transforms()
         for case in sorted(os.listdir(self.evaluate_data_dir)):
             cdir = os.path.join(self.evaluate_data_dir, case)
             if not os.path.isdir(cdir):
@@ -1139,43 +1200,10 @@ class image2label(object):
             image = np.stack(chans, axis=-1)
             # physical voxel size of the input (the reference compares GetPhysicalSize against VolumeThreshold, model.py:117-140)
             spacing = vdata.volume_spacing(os.path.join(cdir, self.evaluate_image_filenames[0]))
-            vt = self.evaluate_volume_threshold if self.evaluate_volume_threshold and self.evaluate_volume_threshold > 0 else None
-            on_device = {}
-            if self.evaluate_lcc or vt is not None:
-                on_device = dict(largest_component=bool(self.evaluate_lcc), volume_threshold=vt, spacing=spacing, extent=chans[0].shape)
-            prepared = None
-            if tf is not None and self.prepare_on_device and self.device.type == "cuda":
-                # EvaluationSetting.PrepareOnDevice: the file goes up once, the pipeline and the window crops run there (None: the
-                # pipeline holds a transform the device path does not serve, and the host path below is kept)
-                from . import prepare as vprep
-                prepared = vprep.prepare_on_device(tf, torch.from_numpy(image).to(self.device), spacing)
-            if prepared is not None:
-                case, _, case_spacing = prepared
-            elif regrid:
-                sample = vtf.run_pipeline(tf, {'image': image, 'label': np.zeros(image.shape[:3], dtype=np.int32), 'spacing': spacing},
-                                          np.random.default_rng(0))
-                case, case_spacing = sample['image'], sample['spacing']
-            else:
-                case = image
-                if tf is not None:
-                    case, _ = vtf.apply_pipeline(tf, image, np.zeros(image.shape[:3], dtype=np.int32), np.random.default_rng(0))
-            if regrid:
-                # the pipeline changes the grid: window on the transformed grid, then back to the input file's size and spacing
-                # (model.py:939-975) before the label filters below, which work in the input's physical units
-                label, softmax = self.evaluate_single_3D(case, back_size=chans[0].shape,
-                                                         back_ratio=vrs.ratios(case_spacing, spacing), **on_device)
-            else:
-                label, softmax = self.evaluate_single_3D(case, **on_device)
-                label = label[tuple(slice(0, n) for n in chans[0].shape)]
-                if softmax is not None:
-                    softmax = softmax[(slice(None),) + tuple(slice(0, n) for n in chans[0].shape)]
+            label, softmax = self.evaluate_case(image, spacing, tf, regrid)
             # the label filters (model.py:1218-1223: largest component, then the volume threshold) ran on the device, on the input's
             # grid, before the label was copied out; the host functions above remain their statement and the route of ops' fallbacks
-            out = os.path.join(cdir, self.evaluate_label_filename)
-            if out.endswith(".npy"):
-                np.save(out, label.astype(np.int16))
-            else:
-                vdata.write_nifti(out[:-3] if out.endswith(".gz") else out, label.astype(np.int16), spacing)
+            self.write_label(os.path.join(cdir, self.evaluate_label_filename), label, spacing)
             if self.evaluate_probability_output:
                 for c in range(softmax.shape[0]):
                     name = self.evaluate_probability_filename

@@ -1885,6 +1885,54 @@ def sample_patch(image, label, start, patch, flip, sigma, seed, out_image, out_l
               "vnet_sample_patch")
 
 
+# ---- scoring a label map against its ground truth (include/vnet_hip_score.h; rules: vnet_tensorflow_amd/score.py) -----------------
+# No autograd.  They launch on the stream the label filters of evaluate launch on, and take their scratch from ops.workspace.
+OVERLAP_MAX_LABELS = 1024  # VNET_OVERLAP_MAX_LABELS
+
+
+def label_overlap(a, b, L):
+    """Per-label overlap counts of two int32 device label maps of one shape, labels 0 .. L - 1: an int64 NumPy array [L + 1, 3], row
+    l < L = {#(a == l and b == l), #(a == l), #(b == l)}, row L = {0, #(a outside [0, L)), #(b outside [0, L))}.  One read-back."""
+    for t in (a, b):
+        _need_gpu(t, "label_overlap", any_dtype=True)
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() == 0:
+            raise VnetHipError("label_overlap: the label maps are contiguous, non-empty int32 tensors, got %s %s" % (t.dtype, tuple(t.shape)))
+    if tuple(a.shape) != tuple(b.shape) or a.device != b.device:
+        raise VnetHipError("label_overlap: maps %s on %s and %s on %s" % (tuple(a.shape), a.device, tuple(b.shape), b.device))
+    L = int(L)
+    if not 1 <= L <= OVERLAP_MAX_LABELS:
+        raise ValueError("label_overlap: 1 <= L <= %d, got %d" % (OVERLAP_MAX_LABELS, L))
+    out = torch.empty((L + 1, 3), dtype=torch.int64, device=a.device)
+    with _Timed("label overlap %d L%d" % (a.numel(), L), 0.0, 8.0 * a.numel()):
+        check(_lib.lib().vnet_label_overlap(_ptr(a), _ptr(b), _ptr(out), a.numel(), L, _stream()), "vnet_label_overlap")
+    return out.cpu().numpy()
+
+
+def component_shapes(label, max_components=4096):
+    """component_table with the index sums that make a centroid of a row: (n, int32 NumPy array [m, 8], int64 NumPy array [m, 3]), m =
+    min(n, max_components); row k = {representative, voxel count, lo[3], hi[3]} of scipy.ndimage.label's component k + 1 of label != 0
+    (int32 [X,Y,Z] on the device), sums[k] = {sum x, sum y, sum z} over its voxels; n is the true number of components also when it
+    exceeds max_components.  Scratch from ops.workspace; the table and the sums come down, nothing else."""
+    X, Y, Z = _sample_label(label, "component_shapes")
+    cap = int(max_components)
+    if cap < 1:
+        raise ValueError("component_shapes: max_components %d" % cap)
+    L = _lib.lib()
+    need = L.vnet_cc_shape_ws_bytes(X, Y, Z)
+    if need == 0:
+        raise VnetHipError("component_shapes: %dx%dx%d has more voxels than an int32 indexes" % (X, Y, Z))
+    ws = workspace(need, label.device)
+    out = torch.empty(cap * CC_ROW + 1, dtype=torch.int32, device=label.device)       # the rows, then n: one copy brings both
+    sums = torch.empty((cap, 3), dtype=torch.int64, device=label.device)
+    with _Timed("cc shape %dx%dx%d" % (X, Y, Z), 0.0, 4.0 * label.numel() * 7):
+        check(L.vnet_cc_shape(_ptr(label), out.data_ptr() + 4 * cap * CC_ROW, _ptr(out), _ptr(sums), cap, X, Y, Z, _ptr(ws), need,
+                              _stream()), "vnet_cc_shape")
+    host = out.cpu().numpy()
+    n = int(host[-1])
+    m = min(n, cap)
+    return n, host[:m * CC_ROW].reshape(-1, CC_ROW).copy(), sums[:m].cpu().numpy()
+
+
 # ---- a case of evaluate on the device (include/vnet_hip_prepare.h; rules: vnet_tensorflow_amd/prepare.py) -------------------------
 # No autograd.  They launch on torch's current stream of the calling thread, like resample.
 STATS_MAX_BLOCKS = 1024    # VNET_STATS_MAX_BLOCKS: a channel's voxels are spread over at most this many blocks of 256 threads
