@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/../vnet_tensorflow_amd/csrc"
 OUT=${1:-../../profiles/r06_check_isa.txt}
 TMP=$(mktemp -d)
-for f in conv_mfma conv_x3 conv_b16 conv2_b16 elementwise input_block pool components sample prepare score deform; do
+for f in conv_mfma conv_x3 conv_b16 conv2_b16 elementwise input_block pool components sample prepare score summary deform; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-function -Wno-unused-result -S --cuda-device-only $f.hip -o $TMP/$f.s 2>/dev/null &
 done
 wait

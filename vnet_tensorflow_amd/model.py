@@ -5,9 +5,10 @@ config.json contract (model.py:185-245) -- on the HIP library instead of a tf.Se
 What is carried over: the graph of model.py:428-568 (network, softmax, one-hot, the Loss.Name
 switch, argmax), the optimiser/LR schedule of model.py:641-666, the step loop of model.py:716-810
 (feed images/labels, dropout from config, batch-statistics BN, one optimiser step, print loss,
-checkpoint cadence, periodic test batch) and the sliding-window inference of model.py:866-937.
-What is not: SimpleITK I/O, its transforms other than `Resample`, TensorBoard
-summaries, the 2-D path.  `sess` is accepted and ignored.
+checkpoint cadence, periodic test batch), the sliding-window inference of model.py:866-937 and the
+TensorBoard summaries of model.py:704-709, 754-755, 793-794 (opt-in: TrainingSetting.SummaryInterval, summary.py).
+What is not: SimpleITK I/O, its transforms other than `Resample`, the 2-D path.  `sess` is accepted
+and ignored.
 """
 import datetime
 import math
@@ -21,6 +22,7 @@ import torch
 
 from . import data as vdata
 from . import networks, ops, optim, parallel
+from . import summary as vsummary
 from ._lib import VnetHipError, check, lib
 
 
@@ -290,6 +292,13 @@ class image2label(object):
         self.epoches = T.get('Epoches', 1)
         self.max_itr = T.get('MaxIterations', 10 ** 12)        # missing from the shipped config.json
         self.log_interval = T.get('LogInterval', 100)
+        # extension (opt-in): TensorBoard event files in LogDir/train and LogDir/test (summary.py).  0: none, as
+        # before; N > 0: a full summary of every training step whose global step is a multiple of N and of every test step
+        # (1 = the reference's cadence, model.py:754, 793); ImageLog adds the image summaries
+        si = T.get('SummaryInterval', 0)
+        if isinstance(si, bool) or not isinstance(si, int) or si < 0:
+            raise SystemExit("Invalid SummaryInterval %r (an integer >= 0; 0 = no event files)" % (si,))
+        self.summary_interval = si
         N = T['Networks']
         self.network_name = N['Name']
         self.dropout_rate = N['Dropout']
@@ -336,7 +345,7 @@ class image2label(object):
         self.prepare_on_device = bool(E.get('PrepareOnDevice', False))
         self._print("{}: Reading configuration file complete".format(_now()))
 
-    # -- reference model.py:297-630 (network + loss head; summaries/metrics not carried) ---------------
+    # -- reference model.py:297-630 (network + loss head; its summaries and metrics: _log_step) ---------------
     @in_context
     def build_model_graph(self):
         self._print("{}: Start to build model graph...".format(_now()))
@@ -415,6 +424,7 @@ class image2label(object):
             return logits, None, sm, pred
         loss, dice, sm, pred = ops.softmax_loss(logits, labels, self.loss_name, self.loss_weights, self.loss_alpha,
                                                 want_softmax=want_softmax, want_pred=want_pred)
+        self._head_dice = dice                 # (the `1.dice` summary of the mixed losses)
         return logits, loss, sm, pred
 
     @in_context
@@ -474,9 +484,10 @@ class image2label(object):
             ops.set_param_grad_stream(False)
 
     # -- one training step (reference model.py:743-748: ONE sess.run per step) ------------------------------------
-    def _compute_gradients(self, images, labels, dropout, split=False):
+    def _compute_gradients(self, images, labels, dropout, split=False, fetch=None):
         """forward, loss, backward (gradients written into the flat buffer), join the parameter-gradient stream.
-        split: stop the backward pass at the network's cut (encoder | bottom level + decoder); _backward_rest() continues."""
+        split: stop the backward pass at the network's cut (encoder | bottom level + decoder); _backward_rest() continues.
+        fetch: a dict that receives this pass's 'softmax', 'pred' and 'dice' (a summary step); None: the loss head forms neither."""
         if hasattr(self.network, "cut_backward"):
             self.network.cut_backward = bool(split)
         if getattr(self.network, "fuse_zero_bias_grad", False):
@@ -484,7 +495,9 @@ class image2label(object):
         else:
             self.flat.zero_grad()
         ops.begin_dropout_pass()
-        _, loss, _, _ = self.forward(images, labels, dropout)
+        _, loss, sm, pred = self.forward(images, labels, dropout, want_softmax=fetch is not None, want_pred=fetch is not None)
+        if fetch is not None:
+            fetch.update(softmax=sm, pred=pred, dice=self._head_dice)
         if getattr(self, "_one", None) is None:
             self._one = torch.ones((), dtype=torch.float32, device=self.device)     # autograd would fill a fresh one every step
         with ops.deferred_wgrad_reduce(self._defer_wgrad_reduce()):
@@ -512,8 +525,10 @@ class image2label(object):
         if not torch.cuda.is_current_stream_capturing():
             self.flat.check_accumulation()
 
-    def _train_step_eager(self, images, labels, dropout):
+    def _train_step_eager(self, images, labels, dropout, fetch=None):
         lr = optim.exponential_decay(self.initial_learning_rate, self.global_step, self.decay_steps, self.decay_factor)
+        if fetch is not None:
+            fetch["lr"] = lr
         if self.sync is not None:
             self.sync.begin_step()
         if dropout > 0.0 and self.device.type == "cuda":
@@ -522,11 +537,11 @@ class image2label(object):
             st = ops.step_state(self.device)
             ops.set_step_state(st, lr, lr, self.global_step)
             with ops.use_step_state(st):
-                loss = self._compute_gradients(images, labels, dropout, split=self._two_pass)
+                loss = self._compute_gradients(images, labels, dropout, split=self._two_pass, fetch=fetch)
                 if self._two_pass:
                     self._backward_rest()
         else:
-            loss = self._compute_gradients(images, labels, dropout, split=self._two_pass)
+            loss = self._compute_gradients(images, labels, dropout, split=self._two_pass, fetch=fetch)
             if self._two_pass:
                 self._backward_rest()
         if self.sync is not None:
@@ -626,6 +641,12 @@ class image2label(object):
         dropout = float(self.dropout_rate if dropout is None else dropout)
         mode = self._graph_mode()
         tuner = None
+        # a summary step is THIS step, enqueued kernel by kernel with the loss head asked for softmax and prediction (a captured graph
+        # may reuse the logits' memory later in the same graph; a second forward pass would update the moving statistics twice and
+        # draw other dropout masks).  Eager and replayed steps compute the same bits, and every rank decides from global_step alone
+        fetch = {} if self._summary_due() else None
+        if fetch is not None:
+            mode = "off"
         if mode == "segmented" and getattr(self, "_graphs", None) is not None:       # (after the warm-up steps and the capture)
             tuner = self._dp_tuner()
             if tuner is not None:
@@ -634,12 +655,104 @@ class image2label(object):
         if self.sync is not None:
             self.sync.hold_all = (mode in ("segmented", "serial"))       # eager: buckets go out from the hooks, overlapping backward
         if mode == "off":
-            loss = self._train_step_eager(images, labels, dropout)
+            loss = self._train_step_eager(images, labels, dropout, fetch)
         else:
             loss = self._train_step_graph(mode, images, labels, dropout)
         if tuner is not None:
             tuner.after()
+        if fetch is not None and self._summary_writers[0] is not None:                # (rank 0 only)
+            self._log_step(self._summary_writers[0], images, labels, loss, fetch)
         return loss
+
+    # -- TensorBoard summaries (reference model.py:315-334, 449-463, 562-626, 644, 704-709; summary.py) --------------------------
+    _summary_on, _summary_writers = False, (None, None)
+
+    def _summary_due(self):
+        """Is the training step about to run one whose summary is written?  (the reference logs the step counter AFTER the step)"""
+        return self._summary_on and (self.global_step + 1) % self.summary_interval == 0
+
+    def _open_summaries(self):
+        """SummaryInterval > 0: every rank takes the summary steps eagerly, rank 0 opens LogDir/train (and LogDir/test with
+        Testing).  A restored run opens a new event file next to the old ones."""
+        self._summary_on = int(getattr(self, "summary_interval", 0)) > 0
+        if self._summary_on and self.rank == 0:
+            self._summary_writers = (vsummary.FileWriter(os.path.join(self.log_dir, "train")),
+                                     vsummary.FileWriter(os.path.join(self.log_dir, "test")) if self.testing else None)
+
+    def _close_summaries(self):
+        writers, self._summary_writers, self._summary_on = self._summary_writers, (None, None), False
+        errors = []
+        for w in writers:
+            if w is not None:
+                try:
+                    w.close()
+                except Exception as e:             # close the other writer too, then report
+                    errors.append(e)
+        if errors:
+            raise errors[0]
+
+    def _render_images(self, images, labels, sm, pred):
+        """{tag: uint8 array} of the image summaries of a batch and the event behind them.  Four launches render every slice into
+        ONE device buffer (ops.summary_slices_*), one asynchronous copy brings it into ONE pinned host buffer; the arrays are views
+        of that buffer, valid once the event has completed -- the writer's worker thread waits for it, this thread does not."""
+        B, X, Y, Z, Cin = (int(v) for v in images.shape)
+        K = int(sm.shape[-1])
+        n = B * X * Y * Z
+        factor = vsummary.index_factor(self.output_channel_num, self.label_classes)
+        sizes = (n * Cin, n, n * K * 3, n)
+        dev = torch.empty(sum(sizes), dtype=torch.uint8, device=images.device)
+        part = []
+        for s in sizes:
+            o = sum(p.numel() for p in part)
+            part.append(dev[o:o + s])
+        ops.summary_slices_intensity(images.to(torch.float32).contiguous(), out=part[0])
+        ops.summary_slices_index(labels.reshape(B, X, Y, Z, 1).to(torch.int32).contiguous(), factor, out=part[1])
+        ops.summary_slices_rainbow(sm.contiguous(), out=part[2])
+        ops.summary_slices_index(pred.reshape(B, X, Y, Z, 1).contiguous(), factor, out=part[3])
+        host = torch.empty(dev.numel(), dtype=torch.uint8, pin_memory=True)
+        host.copy_(dev, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(images.device))
+        flat = host.numpy()
+        o1, o2, o3 = sizes[0], sizes[0] + sizes[1], sizes[0] + sizes[1] + sizes[2]
+        img, lab = flat[:o1].reshape(B, Cin, Z, X, Y), flat[o1:o2].reshape(B, Z, X, Y)
+        rain, prd = flat[o2:o3].reshape(B, K, Z, X, Y, 3), flat[o3:].reshape(B, Z, X, Y)
+        out = {}
+        for b in range(B):
+            for c, f in enumerate(self.image_filenames):
+                out.update(zip(vsummary.image_tags("%s_batch%d" % (f, b), Z), img[b, c]))
+            out.update(zip(vsummary.image_tags("label_batch%d" % b, Z), lab[b]))
+            for k, c in enumerate(self.label_classes):
+                out.update(zip(vsummary.image_tags("softmax_%s_batch%d" % (c, b), Z), rain[b, k]))
+            out.update(zip(vsummary.image_tags("pred_batch%d" % b, Z), prd[b]))
+        return out, ev
+
+    def _log_step(self, writer, images, labels, loss, fetch):
+        """One merged summary of the step that produced `loss` and `fetch` (softmax, pred, dice, lr), under the current global step:
+        the scalars of model.py:529-562, 592-626, 644 and, with ImageLog, the images.  The metrics come from a FRESH
+        ops.StreamingMetrics (the reference re-initialises its local variables before every step, model.py:730, 768); where TF
+        divides 0 by 0 (a class absent from the batch) metrics_from_confusion gives 0.0, and that is written."""
+        sm, pred = fetch["softmax"], fetch["pred"]
+        B, Z = int(images.shape[0]), int(images.shape[3])
+        values, ev = {}, None
+        if self.image_log:
+            values, ev = self._render_images(images, labels, sm, pred)
+        m = ops.StreamingMetrics(self.output_channel_num).update(pred, labels.reshape(pred.shape), sm).result()
+        names = vsummary.scalar_names(self.label_classes, self.loss_name)
+        loss_v = float(loss.detach())
+        values[names["loss"]] = loss_v
+        if "dice" in names:
+            one_minus = 1.0 - float(fetch["dice"].detach())
+            values[names["dice"]] = one_minus
+            values[names["xent"]] = loss_v - one_minus
+        values[names["accuracy"]] = m["accuracy"]
+        for i, c in enumerate(self.label_classes):
+            if i > 0:
+                for what in ("sensitivity", "specificity", "dice", "auc"):
+                    values[names[(what, c)]] = m[i][what]
+        values[names["learning_rate"]] = fetch["lr"]
+        order = vsummary.step_tags(self.image_filenames, self.label_classes, B, Z, self.loss_name, self.image_log)
+        writer.add_summary([(t, values[t]) for t in order], self.global_step, wait=ev)
 
     def _all_ranks_agree(self, ok):
         """True iff `ok` on every rank (data parallel: all ranks must enqueue their steps the same way)."""
@@ -846,6 +959,12 @@ class image2label(object):
     # -- reference model.py:632-815 ---------------------------------------------------------------------------
     @in_context
     def train(self):
+        try:
+            return self._train()
+        finally:
+            self._close_summaries()           # on every way out: the MaxIterations return, an exception, the last epoch
+
+    def _train(self):
         self._print("{}: VNet training start...".format(_now()))
         self.rank, self.local_rank, self.world = parallel.init_from_env()
         self.read_config()
@@ -862,6 +981,7 @@ class image2label(object):
             self.load_checkpoint()
             self._print("{}: Last checkpoint epoch: {}".format(_now(), self.start_epoch))
             self._print("{}: Last checkpoint global step: {}".format(_now(), self.global_step))
+        self._open_summaries()
         train_set = self._dataset(self.train_data_dir, True)
         test_iter = None
         if self.testing:
@@ -928,12 +1048,17 @@ class image2label(object):
                         timage, tlabel = next(test_iter)
                     with torch.no_grad():
                         tl = torch.from_numpy(tlabel).to(self.device)
-                        _, tloss, tsm, tpred = self.forward(torch.from_numpy(timage).to(self.device), tl, 0.0, want_softmax=True, want_pred=True)
+                        timg = torch.from_numpy(timage).to(self.device)
+                        _, tloss, tsm, tpred = self.forward(timg, tl, 0.0, want_softmax=True, want_pred=True)
                         # accuracy + streaming per-class tp/tn/fp/fn, sensitivity, specificity, hard dice, ROC AUC
                         # (tf.metrics.*, reference model.py:588-626)
                         if getattr(self, "metrics", None) is None:
                             self.metrics = ops.StreamingMetrics(self.output_channel_num)
                         self.last_metrics = self.metrics.update(tpred, tl[..., 0], tsm).result()
+                        if self._summary_writers[1] is not None:
+                            lr = optim.exponential_decay(self.initial_learning_rate, self.global_step, self.decay_steps, self.decay_factor)
+                            self._log_step(self._summary_writers[1], timg, tl, tloss,
+                                           {"softmax": tsm, "pred": tpred, "dice": self._head_dice, "lr": lr})
                     self._print('{}: Segmentation testing accuracy: {:.4f} dice: {}'.format(
                         _now(), self.last_metrics["accuracy"],
                         [round(self.last_metrics[c]["dice"], 4) for c in range(self.output_channel_num)]))

@@ -1933,6 +1933,62 @@ def component_shapes(label, max_components=4096):
     return n, host[:m * CC_ROW].reshape(-1, CC_ROW).copy(), sums[:m].cpu().numpy()
 
 
+# ---- the image summaries of a step as uint8 slices (include/vnet_hip_summary.h; rules: vnet_tensorflow_amd/summary.py) ------------
+# No autograd, no scratch.  They launch on torch's current stream of the calling thread.  `out`: None = a new uint8 tensor, or the
+# caller's dense uint8 tensor of exactly the result's size (model.py hands out views of ONE buffer, which then leaves in one copy).
+SUMMARY_MAX_BLOCKS = 4096  # VNET_SUMMARY_MAX_BLOCKS
+
+
+def _summary_args(src, what, dtypes, out, shape_of):
+    _need_gpu(src, what, any_dtype=True)
+    if src.dtype not in dtypes or src.dim() != 5 or src.numel() == 0 or not src.is_contiguous():
+        raise VnetHipError("%s: takes a dense, non-empty [B,X,Y,Z,C] tensor of %s, got %s %s" % (
+            what, " / ".join(str(d).replace("torch.", "") for d in dtypes), src.dtype, tuple(src.shape)))
+    dims = tuple(int(v) for v in src.shape)
+    if src.numel() > 2 ** 31 - 1:
+        raise VnetHipError("%s: %s has more elements than an int32 counts" % (what, dims))
+    shape = shape_of(*dims)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or out.device != src.device or not out.is_contiguous() or out.numel() != math.prod(shape):
+        raise VnetHipError("%s: out is a dense uint8 tensor of %d bytes on the source's device" % (what, math.prod(shape)))
+    return dims, out
+
+
+def summary_slices_intensity(images, out=None):
+    """float32 device tensor [B,X,Y,Z,C] -> uint8 [B,C,Z,X,Y]: plane [b][c][z] is the image of height X and width Y the reference logs
+    for slice z of channel c (tf.cast to uint8: truncation; below 0 and NaN give 0, above 255 gives 255 -- summary.slices_intensity)."""
+    dims, out = _summary_args(images, "summary_slices_intensity", (torch.float32,), out, lambda B, X, Y, Z, C: (B, C, Z, X, Y))
+    with _Timed("summary slices f32 %dx%dx%dx%dx%d" % dims, 0.0, 5.0 * images.numel()):
+        check(_lib.lib().vnet_summary_slices_f32(_ptr(images), _ptr(out), *dims, _stream()), "vnet_summary_slices_f32")
+    return out
+
+
+def summary_slices_index(index, factor, out=None):
+    """int32 (label) or int64 (prediction) device tensor [B,X,Y,Z,C] -> uint8 [B,C,Z,X,Y] = (index * factor) mod 256, the planes
+    as summary_slices_intensity orders them (summary.slices_index; factor: summary.index_factor)."""
+    dims, out = _summary_args(index, "summary_slices_index", (torch.int32, torch.int64), out, lambda B, X, Y, Z, C: (B, C, Z, X, Y))
+    factor = int(factor)
+    if not -2 ** 31 <= factor < 2 ** 31:
+        raise ValueError("summary_slices_index: factor %d is no int32" % factor)
+    L = _lib.lib()
+    with _Timed("summary slices index %dx%dx%dx%dx%d" % dims, 0.0, (index.element_size() + 1.0) * index.numel()):
+        if index.dtype == torch.int32:
+            check(L.vnet_summary_slices_i32(_ptr(index), _ptr(out), factor, *dims, _stream()), "vnet_summary_slices_i32")
+        else:
+            check(L.vnet_summary_slices_i64(_ptr(index), _ptr(out), factor, *dims, _stream()), "vnet_summary_slices_i64")
+    return out
+
+
+def summary_slices_rainbow(softmax, out=None):
+    """float32 device tensor [B,X,Y,Z,K] (the loss head's softmax: fp32 in every ComputeDtype) -> uint8 [B,K,Z,X,Y,3]: the reference's
+    grayscale_to_rainbow, times 255, cast to uint8, every fp32 operation rounded on its own (summary.slices_rainbow)."""
+    dims, out = _summary_args(softmax, "summary_slices_rainbow", (torch.float32,), out, lambda B, X, Y, Z, K: (B, K, Z, X, Y, 3))
+    with _Timed("summary rainbow %dx%dx%dx%dx%d" % dims, 0.0, 7.0 * softmax.numel()):
+        check(_lib.lib().vnet_summary_rainbow_f32(_ptr(softmax), _ptr(out), *dims, _stream()), "vnet_summary_rainbow_f32")
+    return out
+
+
 # ---- a case of evaluate on the device (include/vnet_hip_prepare.h; rules: vnet_tensorflow_amd/prepare.py) -------------------------
 # No autograd.  They launch on torch's current stream of the calling thread, like resample.
 STATS_MAX_BLOCKS = 1024    # VNET_STATS_MAX_BLOCKS: a channel's voxels are spread over at most this many blocks of 256 threads
