@@ -1,6 +1,6 @@
 """ctypes binding of libvnet_hip.so (include/vnet_hip.h, include/vnet_hip_unet.h, include/vnet_hip_head.h,
 include/vnet_hip_resample.h, include/vnet_hip_components.h, include/vnet_hip_deform.h, include/vnet_hip_sample.h,
-include/vnet_hip_prepare.h, include/vnet_hip_score.h, include/vnet_hip_summary.h).
+include/vnet_hip_prepare.h, include/vnet_hip_score.h, include/vnet_hip_summary.h, include/vnet_hip_deform_sample.h).
 
 The library is the product: there is NO fallback.  If the shared object is missing, or a
 kernel reports an error, this module raises -- nothing silently routes to PyTorch or the CPU.
@@ -196,6 +196,11 @@ SIGNATURES_SUMMARY = {
     "vnet_summary_rainbow_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 
+# eleventh public header, include/vnet_hip_deform_sample.h (a training sample cut from a resident case through the deformation)
+SIGNATURES_DEFORM_SAMPLE = {
+    "vnet_deform_sample_patch": (_i, [_vp] * 5 + [_i] * 4 + [_d] * 3 + [_i] * 7 + [_f, _u64, _vp]),
+}
+
 
 class WgradJob(ctypes.Structure):
     """include/vnet_hip.h: vnet_wgrad_job (one layer of vnet_conv_wgrad_b16_group)."""
@@ -255,7 +260,7 @@ def lib():
                 setattr(L, name, _memo(fn))    # pure size queries, asked before every launch: answer repeats from a dict
         for name, (res, args) in list(SIGNATURES_UNET.items()) + list(SIGNATURES_HEAD.items()) + list(SIGNATURES_RESAMPLE.items()) + \
                 list(SIGNATURES_COMPONENTS.items()) + list(SIGNATURES_DEFORM.items()) + list(SIGNATURES_SAMPLE.items()) + list(SIGNATURES_PREPARE.items()) + \
-                list(SIGNATURES_SCORE.items()) + list(SIGNATURES_SUMMARY.items()):
+                list(SIGNATURES_SCORE.items()) + list(SIGNATURES_SUMMARY.items()) + list(SIGNATURES_DEFORM_SAMPLE.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
             if name in ("vnet_bn_head_ok", "vnet_bn_head_stats_rows", "vnet_bn_head_ws_bytes", "vnet_cc_ws_bytes", "vnet_cc_table_ws_bytes",

@@ -13,6 +13,7 @@
 // every 1024 voxels and cap the occupancy at three workgroups per CU.
 #include <math.h>
 #include "common.h"
+#include "bspline_field.h"        // bs_axis, bs_row_sum, bs_displacement, df_axis, df_blend, df_out (shared with deform_sample.hip)
 #include "../../include/vnet_hip_deform.h"
 
 // equal neighbours must give exactly their value, and the weights must be those of the NumPy restatement bit for bit: no FMA contraction
@@ -22,50 +23,12 @@ namespace {
 
 constexpr int DF_BLOCK = 256, DF_MAXBLK = 4096;      // (the block and the grid cap of resample.hip and pool.hip)
 constexpr int DF_ROWS = 8, DF_CHUNK = 1024;          // a chunk: clamp(DF_CHUNK / Z, 1, DF_ROWS) z-rows
-constexpr int G = VNET_BSPLINE_GRID, G3 = G * G * G;
 
 struct DeformP {
     const void* x; void* y; const double* coef;
     int X, Y, Z, C, rows;
     double sx, sy, sz;
 };
-
-// one axis of a voxel on the control grid: first control index of the cubic support, the four weights, the valid-region test
-struct BsAxis { int m; double w[4]; bool ok; };
-
-__device__ __forceinline__ BsAxis bs_axis(int i, double s, int n) {
-    const double D = (double)n * s / 10.0, u = ((double)i * s) / D, f = floor(u);
-    BsAxis a;
-    a.ok = u >= 0.0 && u < 10.0;                     // ITK: 1 <= u + 1 < 11 (true for every voxel centre)
-    a.m = a.ok ? min((int)f, 9) : 0;                 // taps m .. m + 3 stay inside 0 .. 12
-    const double t = u - f, t2 = t * t, t3 = t2 * t, o = 1.0 - t;
-    a.w[0] = o * o * o / 6.0;
-    a.w[1] = ((3.0 * t3 - 6.0 * t2) + 4.0) / 6.0;
-    a.w[2] = (((-3.0 * t3 + 3.0 * t2) + 3.0 * t) + 1.0) / 6.0;
-    a.w[3] = t3 / 6.0;
-    return a;
-}
-
-// one axis of the source position: the two neighbours, the weight of the upper one, the inside test -0.5 <= c < n - 0.5
-struct DfAxis { int lo, hi; double d; bool in; };
-
-__device__ __forceinline__ DfAxis df_axis(double c, int n) {
-    const double f = floor(c);
-    DfAxis a;
-    a.in = c >= -0.5 && c < (double)n - 0.5;         // (false for a NaN)
-    const int b = a.in ? (int)f : 0;                 // inside: -1 <= f <= n - 1; outside c may exceed the int range
-    a.lo = b > 0 ? b : 0;
-    a.hi = b + 1 < n ? b + 1 : n - 1;
-    a.d = c - f;
-    return a;
-}
-
-__device__ __forceinline__ double df_lerp(double lo, double hi, double d) { return lo + d * (hi - lo); }
-
-__device__ __forceinline__ float df_out(double v, float) { return (float)v; }
-__device__ __forceinline__ int df_out(double v, int) {          // static_cast<int> after clamping: truncation toward zero
-    return v <= -2147483648.0 ? (int)0x80000000 : v >= 2147483647.0 ? 0x7fffffff : (int)v;
-}
 
 // T: float (image) or int (label map, C = 1).  VEC: the channels of a voxel go in quads, else one by one.
 template <typename T, bool VEC>
@@ -83,18 +46,7 @@ __global__ void __launch_bounds__(DF_BLOCK) bspline_deform_kernel(DeformP p) {
             const int r = it / (3 * G), q = it - r * (3 * G), a = q / G, k = q - a * G;
             const int row = row0 + r, ix = row / p.Y, iy = row - ix * p.Y;
             const BsAxis ax = bs_axis(ix, p.sx, p.X), ay = bs_axis(iy, p.sy, p.Y);
-            double acc = 0.0;
-            if (ax.ok && ay.ok) {
-                const double* c = coef + a * G3 + (k * G + ay.m) * G + ax.m;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    double s = 0.0;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) s += ax.w[i] * c[j * G + i];
-                    acc += ay.w[j] * s;
-                }
-            }
-            S[r][a][k] = acc;
+            S[r][a][k] = bs_row_sum(coef, a, k, ax, ay);
         }
         __syncthreads();
         for (int v = threadIdx.x; v < nrows * p.Z; v += DF_BLOCK) {
@@ -102,13 +54,7 @@ __global__ void __launch_bounds__(DF_BLOCK) bspline_deform_kernel(DeformP p) {
             const int row = row0 + r, ix = row / p.Y, iy = row - ix * p.Y;
             const BsAxis az = bs_axis(iz, p.sz, p.Z);
             double d[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                double s = 0.0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) s += az.w[k] * S[r][a][az.m + k];
-                d[a] = az.ok ? s : 0.0;
-            }
+            bs_displacement(S[r], az, d);
             const DfAxis sx = df_axis((double)ix + d[0] / p.sx, p.X), sy = df_axis((double)iy + d[1] / p.sy, p.Y),
                          sz = df_axis((double)iz + d[2] / p.sz, p.Z);
             const bool in = sx.in && sy.in && sz.in;
@@ -135,9 +81,7 @@ __global__ void __launch_bounds__(DF_BLOCK) bspline_deform_kernel(DeformP p) {
                     }
 #pragma unroll
                     for (int w = 0; w < W; ++w) {
-                        const double z00 = df_lerp(t[0][w], t[1][w], sz.d), z01 = df_lerp(t[2][w], t[3][w], sz.d);
-                        const double z10 = df_lerp(t[4][w], t[5][w], sz.d), z11 = df_lerp(t[6][w], t[7][w], sz.d);
-                        res[w] = df_out(df_lerp(df_lerp(z00, z01, sy.d), df_lerp(z10, z11, sy.d), sx.d), T());
+                        res[w] = df_out(df_blend(t[0][w], t[1][w], t[2][w], t[3][w], t[4][w], t[5][w], t[6][w], t[7][w], sx.d, sy.d, sz.d), T());
                     }
                 }
                 if constexpr (VEC) *reinterpret_cast<float4*>(y + out + (size_t)cu * 4) = make_float4(res[0], res[1], res[2], res[3]);
@@ -149,11 +93,8 @@ __global__ void __launch_bounds__(DF_BLOCK) bspline_deform_kernel(DeformP p) {
 }
 
 inline int df_check(const void* x, const void* y, const double* coef, int X, int Y, int Z, int C, double sx, double sy, double sz) {
-    if (!x || !y || !coef || X < 1 || Y < 1 || Z < 1 || C < 1 || !isfinite(sx) || !isfinite(sy) || !isfinite(sz) ||
-        !(sx > 0.0) || !(sy > 0.0) || !(sz > 0.0)) return VNET_E_BADARG;
-    const unsigned long long xy = (unsigned long long)X * (unsigned long long)Y;
-    if (xy > 0x7fffffffull || xy * (unsigned long long)Z > 0x7fffffffull) return VNET_E_UNSUPPORTED;      // int32 voxel index
-    return 0;
+    if (!x || !y || !coef) return VNET_E_BADARG;
+    return df_check_grid(X, Y, Z, C, sx, sy, sz);
 }
 
 template <typename T>

@@ -12,6 +12,7 @@
 #include <limits.h>
 #include "common.h"
 #include "cc_table.h"
+#include "philox_noise.h"          // philox4x32_10, box_muller, sp_noise_quad / sp_noise_one, sp_bad_window (shared with deform_sample.hip)
 #include "../../include/vnet_hip_components.h"
 #include "../../include/vnet_hip_sample.h"
 
@@ -49,27 +50,6 @@ struct SampleP {
     unsigned k0, k1;
 };
 
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// one Box-Muller pair from two words (precise logf / sqrtf / cosf / sinf)
-__device__ __forceinline__ void box_muller(unsigned ka, unsigned kb, float& zc, float& zs) {
-    const float u1 = ((float)(ka >> 9) + 0.5f) * 1.1920928955078125e-07f;       // 2^-23
-    const float u2 = (float)(kb >> 8) * 5.9604644775390625e-08f;                // 2^-24
-    const float r = sqrtf(-2.0f * logf(u1));
-    const float th = 6.2831855f * u2;
-    zc = r * cosf(th);
-    zs = r * sinf(th);
-}
-
 // VEC: a unit is 4 consecutive channels of one output voxel, else one channel.  NOISE false: the crop bit for bit.
 template <bool VEC, bool NOISE>
 __global__ void __launch_bounds__(SP_BLOCK) sample_patch_kernel(SampleP p) {
@@ -91,32 +71,15 @@ __global__ void __launch_bounds__(SP_BLOCK) sample_patch_kernel(SampleP p) {
         if (cu == 0) yl[ov] = l[iv];
         if constexpr (VEC) {
             float4 f = *reinterpret_cast<const float4*>(x + iv * p.C + (size_t)cu * 4);
-            if constexpr (NOISE) {
-                unsigned k[4];
-                philox4x32_10((unsigned)idx, (unsigned)((u64)idx >> 32), 0u, 0u, p.k0, p.k1, k);     // (idx IS the group index q here)
-                float z0, z1, z2, z3;
-                box_muller(k[0], k[1], z0, z1);
-                box_muller(k[2], k[3], z2, z3);
-                f.x = fmaf(p.sigma, z0, f.x); f.y = fmaf(p.sigma, z1, f.y); f.z = fmaf(p.sigma, z2, f.z); f.w = fmaf(p.sigma, z3, f.w);
-            }
+            if constexpr (NOISE) f = sp_noise_quad(f, idx, p.sigma, p.k0, p.k1);               // (idx IS the group index q here)
             reinterpret_cast<float4*>(y)[idx] = f;
         } else {
             float f = x[iv * p.C + cu];
-            if constexpr (NOISE) {
-                const u64 q = (u64)idx >> 2;
-                const int j = (int)(idx & 3);
-                unsigned k[4];
-                philox4x32_10((unsigned)q, (unsigned)(q >> 32), 0u, 0u, p.k0, p.k1, k);
-                float zc, zs;
-                box_muller((j & 2) ? k[2] : k[0], (j & 2) ? k[3] : k[1], zc, zs);
-                f = fmaf(p.sigma, (j & 1) ? zs : zc, f);
-            }
+            if constexpr (NOISE) f = sp_noise_one(f, idx, p.sigma, p.k0, p.k1);
             y[idx] = f;
         }
     }
 }
-
-inline bool sp_bad_window(int n, int s, int w) { return s < 0 || w < 1 || s > n - w; }
 
 }  // namespace
 

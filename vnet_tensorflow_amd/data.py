@@ -175,15 +175,20 @@ class VolumeDataset(object):
         # device_tail (a torch device; TrainingSetting.SampleOnDevice): prepared cases -- the case after the pipeline's deterministic
         # prefix -- live in device memory under an LRU byte budget, the random tail's index decisions stay on the host and one kernel
         # writes each sample into a device batch (vnet_tensorflow_amd/sample.py).  Only the tails
-        # transforms.plan_tail recognises; any other keeps the loader path below
-        self.device_tail, self._tail = None, None
+        # transforms.plan_tail recognises, and those with one BSplineDeformation in front (transforms.plan_deformed_tail: the label is
+        # deformed and its components tabled per visit, the image is deformed by the kernel that writes the sample, for the window's
+        # voxels alone); any other keeps the loader path below
+        self.device_tail, self._tail, self._deformed = None, None, False
         if device_tail is not None:
-            from .transforms import deterministic_prefix, plan_tail
+            from .transforms import deterministic_prefix, plan_deformed_tail, plan_tail
             self._tail_at = deterministic_prefix(transforms) if transforms is not None else 0
             self._tail = plan_tail(transforms[self._tail_at:]) if transforms is not None else None
+            if self._tail is None and transforms is not None:
+                self._tail = plan_deformed_tail(transforms[self._tail_at:])
+                self._deformed = self._tail is not None
             if self._tail is None:
-                print("VolumeDataset: the pipeline's random tail is not one the device serves (ConfidenceCrop2 | RandomCrop, then "
-                      "RandomFlip, then RandomNoise); samples keep the loader path")
+                print("VolumeDataset: the pipeline's random tail is not one the device serves ([BSplineDeformation,] ConfidenceCrop2 | "
+                      "RandomCrop, then RandomFlip, then RandomNoise); samples keep the loader path")
             elif tuple(self._tail.crop.output_size) != self.patch:
                 raise ValueError("the pipeline's crop produces %s samples, PatchShape is %s" % (tuple(self._tail.crop.output_size), self.patch))
             else:
@@ -191,9 +196,13 @@ class VolumeDataset(object):
                 import torch
                 self.device_tail = torch.device(device_tail)
                 self.device_cache_bytes, self.max_components = int(device_cache_bytes), int(max_components)
-                # case -> (image, label, (n, rows) | None) on the device, least recently used first.  No lock of its own: it is
+                # case -> (image, label, (n, rows) | None, spacing) on the device, least recently used first.  No lock of its own: it is
                 # touched only inside ops.side_work, whose lock is exclusive (one loader thread at a time, and never during a capture)
                 self._dev_cache, self._dev_bytes, self._dev_host_only = collections.OrderedDict(), 0, set()
+                # (its bookkeeping -- look-up, evictions, insertion -- is atomic all the same: under a side_work that excludes nobody, the
+                # CPU stand-ins of the tests, two loader threads must not both evict and then both insert)
+                import threading
+                self._dev_lock = threading.Lock()
                 self.device_stats = {"uploads": 0, "evictions": 0, "host_samples": 0}
         if self.train and self.steps_per_epoch() == 0:
             raise ValueError("%d cases give no full batch for %d rank(s) x batch %d: every rank needs at least one batch per "
@@ -271,10 +280,15 @@ class VolumeDataset(object):
         return run_pipeline(self.transforms[:self._tail_at], {'image': image, 'label': label, 'spacing': self._spacing(case)}, None)
 
     def _device_case(self, case):
-        """(image float32 [X,Y,Z,C], label int32 [X,Y,Z], component table | None) on the device, or None when the case takes the NumPy
-        path: larger than the budget, or more components than max_components.  Called inside ops.side_work.  The table belongs to the
-        prepared case -- a pure function of the file and the deterministic prefix -- so it is computed once, at the upload, and leaves
-        the cache with the case."""
+        """(image float32 [X,Y,Z,C], label int32 [X,Y,Z], component table | None, spacing) on the device, or None when the case takes the
+        NumPy path: larger than the budget, or more components than max_components.  Called inside ops.side_work.  The table belongs to
+        the prepared case -- a pure function of the file and the deterministic prefix -- so it is computed once, at the upload, and
+        leaves the cache with the case.  Behind a deformation there is no such table: the components are those of the deformed label,
+        which differ from visit to visit (_deformed_sample)."""
+        with self._dev_lock:
+            return self._device_case_locked(case)
+
+    def _device_case_locked(self, case):
         import torch
         from . import ops
         from .transforms import ConfidenceCrop2
@@ -297,25 +311,69 @@ class VolumeDataset(object):
             self.device_stats["evictions"] += 1
         di, dl = torch.from_numpy(image).to(self.device_tail), torch.from_numpy(label).to(self.device_tail)
         table = None
-        if isinstance(self._tail.crop, ConfidenceCrop2):
+        if isinstance(self._tail.crop, ConfidenceCrop2) and not self._deformed:
             need = ops._lib.lib().vnet_cc_table_ws_bytes(*label.shape)
             ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device_tail)     # (this thread's, on its side stream)
             table = ops.component_table(dl, self.max_components, ws=ws)
             if table[0] > self.max_components:
                 self._dev_host_only.add(case)
                 return None
-        entry = (di, dl, table)
+        entry = (di, dl, table, tuple(float(v) for v in sample.get('spacing', (1.0, 1.0, 1.0))))
         self._dev_cache[case] = entry
         self._dev_bytes += nbytes
         self.device_stats["uploads"] += 1
         return entry
+
+    class _TooManyComponents(Exception):
+        pass
+
+    def _deformed_sample(self, entry, rng, out_image, out_label):
+        """One sample through the deformation, inside ops.side_work: the coefficients go up (52 KB, pinned staging), the LABEL is deformed
+        whole -- the crop decides on it -- into a volume of this thread, its components are tabled for ConfidenceCrop2, the draws are
+        made, and one kernel deforms the window's voxels of the resident image into the slot.  Transient per loader thread: the deformed
+        label (4 B/voxel) and the table's scratch (8 B/voxel).  Raises _TooManyComponents (after the coefficients were drawn) when the
+        deformed label holds more than max_components components."""
+        import torch
+        from . import ops
+        from .transforms import ConfidenceCrop2
+        di, dl, _, spacing = entry
+        shape = tuple(dl.shape)
+        state = {}
+
+        def deformed(coef):
+            # (the staging buffer is this thread's and is written again by its next sample: every sample ends in a read-back -- the
+            # table's or a window count's -- or in the synchronise of side_work, behind this copy on the same stream)
+            hc = ops.pinned_staging("deform_sample.coef", coef.shape, torch.float64)
+            np.copyto(hc.numpy(), coef)
+            dc = state["coef"] = hc.to(self.device_tail, non_blocking=True)
+            yl = state["label"] = ops.bspline_deform(dl, dc, spacing, "label")
+            table = None
+            if isinstance(self._tail.crop, ConfidenceCrop2):
+                need = ops._lib.lib().vnet_cc_table_ws_bytes(*shape)
+                ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device_tail)
+                table = ops.component_table(yl, max(self.max_components, 1), ws=ws)
+                if table[0] > self.max_components:
+                    raise VolumeDataset._TooManyComponents()
+            return (lambda: table), (lambda s, n, lo, hi: ops.window_count(yl, s, n, lo, hi))
+        _, start, mask, sigma, seed = self._tail.draw(shape, rng, deformed)
+        ops.deform_sample_patch(di, state["label"], state["coef"], spacing, start, self.patch, mask, sigma, seed, out_image, out_label)
+
+    def _host_sample(self, case, rng, out_image, out_label):
+        """The NumPy tail of one sample, copied into its slot of the device batch."""
+        import torch
+        from .transforms import run_pipeline
+        self.device_stats["host_samples"] += 1
+        sample = run_pipeline(self.transforms[self._tail_at:], self._prepared_split(case), rng)
+        if tuple(sample['label'].shape) != self.patch:
+            raise ValueError("the transform pipeline produced a %s sample, PatchShape is %s" % (tuple(sample['label'].shape), self.patch))
+        out_image.copy_(torch.from_numpy(np.ascontiguousarray(sample['image'], dtype=np.float32)))
+        out_label[..., 0].copy_(torch.from_numpy(np.ascontiguousarray(sample['label'], dtype=np.int32)))
 
     def _make_batch_device(self, cases, seeds):
         """Device tensors (image float32 [B,*P,Cin], label int32 [B,*P,1]); wholly inside ops.side_work: the loader thread's
         uploads, launches and read-backs run on its own stream and never while the step graph is being captured."""
         import torch
         from . import ops
-        from .transforms import run_pipeline
         si, sl = (len(cases),) + self.batch_shapes()[0][1:], (len(cases),) + self.batch_shapes()[1][1:]
         with ops.side_work(self.device_tail):
             img = torch.empty(si, dtype=torch.float32, device=self.device_tail)
@@ -324,18 +382,20 @@ class VolumeDataset(object):
                 rng = np.random.default_rng(sd)
                 entry = self._device_case(case)
                 if entry is None:
-                    self.device_stats["host_samples"] += 1
-                    sample = run_pipeline(self.transforms[self._tail_at:], self._prepared_split(case), rng)
-                    if tuple(sample['label'].shape) != self.patch:
-                        raise ValueError("the transform pipeline produced a %s sample, PatchShape is %s" % (tuple(sample['label'].shape), self.patch))
-                    img[i].copy_(torch.from_numpy(np.ascontiguousarray(sample['image'], dtype=np.float32)))
-                    lab[i, ..., 0].copy_(torch.from_numpy(np.ascontiguousarray(sample['label'], dtype=np.int32)))
+                    self._host_sample(case, rng, img[i], lab[i])
                     continue
-                di, dl, table = entry
+                di, dl, table, _ = entry
                 shape = tuple(dl.shape)
                 if any(s < p for s, p in zip(shape, self.patch)):
                     raise ValueError("the prepared case is %s, smaller than PatchShape %s (put a Padding in front of the crop, like "
                                      "the reference's pipeline3D.yaml)" % (shape, self.patch))
+                if self._deformed:
+                    try:
+                        self._deformed_sample(entry, rng, img[i], lab[i])
+                    except VolumeDataset._TooManyComponents:
+                        # the coefficients were drawn from `rng` already: the NumPy tail starts over on a generator of its own
+                        self._host_sample(case, np.random.default_rng(sd), img[i], lab[i])
+                    continue
                 start, mask, sigma, seed = self._tail.draw(shape, rng, lambda: table,
                                                            lambda s, n, lo, hi: ops.window_count(dl, s, n, lo, hi))
                 ops.sample_patch(di, dl, start, self.patch, mask, sigma, seed, img[i], lab[i])

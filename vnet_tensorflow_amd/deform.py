@@ -64,14 +64,35 @@ def _dense(n, spacing):
     return A, valid
 
 
-def displacement(shape, spacing, coef):
+def _window(shape, window):
+    """The slices of `window` = (start, size) inside a volume of `shape`; None is the whole volume."""
+    if window is None:
+        return tuple(slice(0, int(n)) for n in shape)
+    start, size = (tuple(int(v) for v in w) for w in window)
+    if len(start) != 3 or len(size) != 3 or any(s < 0 or w < 1 or s + w > int(n) for s, w, n in zip(start, size, shape)):
+        raise ValueError("bspline_deform: window %s + %s does not lie inside the volume %s" % (start, size, tuple(shape)))
+    return tuple(slice(s, s + w) for s, w in zip(start, size))
+
+
+def displacement(shape, spacing, coef, window=None):
     """float64 [X,Y,Z,3]: the displacement (physical units, components x, y, z) at every voxel centre, evaluated separably: one contraction
-    per axis, x first, then y, then z."""
+    per axis, x first, then y, then z.  window = (start, size): only the voxels of that window of the volume, [*size, 3] -- the control
+    grid and the valid region stay those of `shape`; only the rows of the three weight matrices are restricted."""
     coef, spacing = _coef(coef), _spacing(spacing)
-    (Ax, vx), (Ay, vy), (Az, vz) = (_dense(int(n), s) for n, s in zip(shape, spacing))
-    t = np.einsum("xi,akji->akjx", Ax, coef)
-    t = np.einsum("yj,akjx->akxy", Ay, t)
-    d = np.einsum("zk,akxy->xyza", Az, t)
+    (Ax, vx), (Ay, vy), (Az, vz) = ((A[w], v[w]) for (A, v), w in zip((_dense(int(n), s) for n, s in zip(shape, spacing)), _window(shape, window)))
+    # each contraction adds its 13 terms in ascending control index, one array operation per term: the order of a voxel's sum does not
+    # depend on how many voxels are evaluated with it (np.einsum picks its loop order by the operands' shapes: a window one voxel wide
+    # came out an ulp away from the same voxels of the whole volume).  Off the support the weights are exact zeros, so this is also the
+    # order of the kernels: ((w0 c0 + w1 c1) + w2 c2) + w3 c3 over the four taps, x first, then y, then z
+    t1 = np.zeros(coef.shape[:3] + (Ax.shape[0],), dtype=np.float64)                   # [a, k, j, x]
+    for i in range(GRID):
+        t1 += Ax[None, None, None, :, i] * coef[..., i, None]
+    t2 = np.zeros(coef.shape[:2] + (Ax.shape[0], Ay.shape[0]), dtype=np.float64)      # [a, k, x, y]
+    for j in range(GRID):
+        t2 += Ay[None, None, None, :, j] * t1[:, :, j, :, None]
+    d = np.zeros((Ax.shape[0], Ay.shape[0], Az.shape[0], 3), dtype=np.float64)
+    for k in range(GRID):
+        d += Az[None, None, :, k, None] * np.moveaxis(t2[:, k], 0, -1)[:, :, None, :]
     ok = vx[:, None, None] & vy[None, :, None] & vz[None, None, :]
     return np.where(ok[..., None], d, 0.0)
 
@@ -92,11 +113,12 @@ def displacement_direct(shape, spacing, coef):
     return np.where(ok[..., None], d, 0.0)
 
 
-def source_index(shape, spacing, coef):
-    """float64 [X,Y,Z,3]: the continuous source index c_a = i_a + d_a / s_a of every voxel."""
+def source_index(shape, spacing, coef, window=None):
+    """float64 [X,Y,Z,3]: the continuous source index c_a = i_a + d_a / s_a of every voxel (window: of the window's voxels alone; the
+    indices are those of the volume)."""
     spacing = _spacing(spacing)
-    d = displacement(shape, spacing, coef)
-    grid = np.meshgrid(*(np.arange(int(n), dtype=np.float64) for n in shape), indexing="ij")
+    d = displacement(shape, spacing, coef, window)
+    grid = np.meshgrid(*(np.arange(w.start, w.stop, dtype=np.float64) for w in _window(shape, window)), indexing="ij")
     return np.stack([g + d[..., a] / spacing[a] for a, g in enumerate(grid)], axis=-1)
 
 
@@ -111,16 +133,17 @@ def undecidable(shape, spacing, coef, eps=1e-9):
     return bad
 
 
-def linear64(x, coef, spacing):
+def linear64(x, coef, spacing, window=None):
     """x [X,Y,Z] or [X,Y,Z,C] (any dtype) -> float64 of the same shape: the 8-tap blend at the deformed position, before its one
-    conversion to the output type; 0 outside."""
+    conversion to the output type; 0 outside.  window = (start, size): only the voxels of that window are evaluated, [*size(, C)]; their
+    taps are gathered from the whole of x and the inside test is that of the volume."""
     x = np.asarray(x)
     if x.ndim not in (3, 4) or min(x.shape[:3]) < 1:
         raise ValueError("bspline_deform: takes a non-empty [X,Y,Z] or [X,Y,Z,C] volume, got %s" % (x.shape,))
     shape = x.shape[:3]
-    c = source_index(shape, spacing, coef)
+    c = source_index(shape, spacing, coef, window)
     v = x.astype(np.float64).reshape(shape + (-1,))
-    inside = np.ones(shape, dtype=bool)
+    inside = np.ones(c.shape[:3], dtype=bool)
     lo, hi, d = [], [], []
     for a, n in enumerate(shape):
         ca = c[..., a]
@@ -140,7 +163,7 @@ def linear64(x, coef, spacing):
     z00, z01 = lerp(tap(0, 0, 0), tap(0, 0, 1), d[2]), lerp(tap(0, 1, 0), tap(0, 1, 1), d[2])
     z10, z11 = lerp(tap(1, 0, 0), tap(1, 0, 1), d[2]), lerp(tap(1, 1, 0), tap(1, 1, 1), d[2])
     out = lerp(lerp(z00, z01, d[1]), lerp(z10, z11, d[1]), d[0])
-    return np.where(inside[..., None], out, 0.0).reshape(x.shape)
+    return np.where(inside[..., None], out, 0.0).reshape(c.shape[:3] + x.shape[3:])
 
 
 def linear(image, coef, spacing):

@@ -1885,6 +1885,56 @@ def sample_patch(image, label, start, patch, flip, sigma, seed, out_image, out_l
               "vnet_sample_patch")
 
 
+def deform_sample_patch(image, deformed_label, coef, spacing, start, patch, flip, sigma, seed, out_image, out_label):
+    """One sample of a batch cut THROUGH the free-form deformation, written in place (include/vnet_hip_deform_sample.h): out_image
+    (float32 [P0,P1,P2,C]) gets, bit for bit, what sample_patch(bspline_deform(image, coef, spacing), ...) writes for the same window,
+    flip, sigma and seed -- only the window's voxels are deformed, the deformed image is never formed --, out_label (int32 [P0,P1,P2] or
+    [P0,P1,P2,1]) the flipped window of deformed_label, the caller's bspline_deform(label, coef, spacing, "label").  image is the
+    UNDEFORMED case (float32 [X,Y,Z,C]); coef the 6591 doubles of the control grid, a float64 tensor on the image's device.  The
+    restatement is vnet_tensorflow_amd.sample.deform_patch.  On meta tensors: the checks of shapes and dtypes, nothing written."""
+    spacing = tuple(float(v) for v in spacing)
+    if len(spacing) != 3:
+        raise ValueError("deform_sample_patch: spacing takes three values")
+    start, patch = _three(start, "deform_sample_patch: start"), _three(patch, "deform_sample_patch: patch")
+    tensors = (image, deformed_label, coef, out_image, out_label)
+    meta = _meta(*tensors)
+    if meta and not all(t.device.type == "meta" for t in tensors):
+        raise VnetHipError("deform_sample_patch: meta tensors go with meta tensors")
+    if not meta:
+        for t in (image, out_image):
+            _need_gpu(t, "deform_sample_patch")
+        for t in (deformed_label, coef, out_label):
+            _need_gpu(t, "deform_sample_patch", any_dtype=True)
+    if deformed_label.dim() != 3 or deformed_label.numel() == 0 or deformed_label.dtype != torch.int32 or out_label.dtype != torch.int32:
+        raise VnetHipError("deform_sample_patch: the label map is a non-empty int32 [X,Y,Z] tensor and out_label int32, got %s %s / %s" % (
+            deformed_label.dtype, tuple(deformed_label.shape), out_label.dtype))
+    if image.dtype != torch.float32 or out_image.dtype != torch.float32:
+        raise VnetHipError("deform_sample_patch: expected float32, got %s / %s" % (image.dtype, out_image.dtype))
+    X, Y, Z = (int(v) for v in deformed_label.shape)
+    if image.dim() != 4 or tuple(image.shape[:3]) != (X, Y, Z):
+        raise VnetHipError("deform_sample_patch: image %s does not go with label %s" % (tuple(image.shape), (X, Y, Z)))
+    C = int(image.shape[3])
+    if coef.dtype != torch.float64 or coef.numel() != 3 * 13 ** 3:
+        raise VnetHipError("deform_sample_patch: the control grid is %d float64 values, got %d %s" % (3 * 13 ** 3, coef.numel(), coef.dtype))
+    if tuple(out_image.shape) != patch + (C,) or tuple(out_label.shape) not in (patch, patch + (1,)):
+        raise VnetHipError("deform_sample_patch: outputs %s / %s for a patch %s of %d channel(s)" % (
+            tuple(out_image.shape), tuple(out_label.shape), patch, C))
+    if not all(t.is_contiguous() for t in tensors):
+        raise VnetHipError("deform_sample_patch: image, label, control grid and both slots are dense")
+    if any(s < 0 or s + p > n for s, p, n in zip(start, patch, (X, Y, Z))):
+        raise ValueError("deform_sample_patch: window %s + %s leaves the volume %s" % (start, patch, (X, Y, Z)))
+    if not all(math.isfinite(s) and s > 0 for s in spacing):
+        raise ValueError("deform_sample_patch: spacing must be three finite positive values, got %s" % (spacing,))
+    if meta:
+        return
+    # 8 taps per element at worst (neighbouring voxels share them through the caches), the label window, both outputs
+    with _Timed("deform sample patch %dx%dx%d %d" % (patch + (C,)), 0.0, 36.0 * out_image.numel() + 8.0 * out_label.numel()):
+        check(_lib.lib().vnet_deform_sample_patch(_ptr(image), _ptr(deformed_label), _ptr(coef), _ptr(out_image), _ptr(out_label),
+                                                  X, Y, Z, C, *spacing, *start, *patch, int(flip), float(sigma),
+                                                  int(seed) & (2 ** 64 - 1), _thread_stream(image.device)),
+              "vnet_deform_sample_patch")
+
+
 # ---- scoring a label map against its ground truth (include/vnet_hip_score.h; rules: vnet_tensorflow_amd/score.py) -----------------
 # No autograd.  They launch on the stream the label filters of evaluate launch on, and take their scratch from ops.workspace.
 OVERLAP_MAX_LABELS = 1024  # VNET_OVERLAP_MAX_LABELS

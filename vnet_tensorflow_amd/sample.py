@@ -66,6 +66,25 @@ def patch(image, label, start, size, flip=0, sigma=0.0, seed=0):
     return img, np.ascontiguousarray(lab)
 
 
+def deform_patch(image, label, coef, spacing, start, size, flip=0, sigma=0.0, seed=0):
+    """The sample vnet_deform_sample_patch writes (include/vnet_hip_deform_sample.h) from the UNDEFORMED case: what
+    patch(deform.linear(image, coef, spacing), deform.label(label, coef, spacing), start, size, flip, sigma, seed) returns, evaluated
+    for the voxels of the window alone -- deform.linear64 restricted to the window: the displacement from the rows of the volume's
+    weight matrices that belong to it, the taps gathered from the whole volume, the inside test against the volume."""
+    from . import deform as D
+    image, label = np.asarray(image), np.asarray(label)
+    if image.ndim != 4 or label.ndim != 3 or image.shape[:3] != label.shape or not np.issubdtype(label.dtype, np.integer):
+        raise ValueError("deform_patch: image [X,Y,Z,C] and an integer label [X,Y,Z] of one grid, got %s / %s %s" % (image.shape, label.dtype, label.shape))
+    window = (tuple(int(s) for s in start), tuple(int(n) for n in size))
+    img = D.linear64(image, coef, spacing, window).astype(np.float32)
+    info = np.iinfo(label.dtype)
+    lab = np.clip(np.trunc(D.linear64(label, coef, spacing, window)), info.min, info.max).astype(label.dtype)
+    img, lab = np.ascontiguousarray(np.flip(img, flip_axes(flip))), np.ascontiguousarray(np.flip(lab, flip_axes(flip)))
+    if sigma:
+        img = img.astype(np.float64) + float(sigma) * normal(seed, img.size).reshape(img.shape)
+    return img, lab
+
+
 def component_table(label):
     """(n, int32 [n, ROW]) of label != 0 from ndimage.label + find_objects."""
     from scipy import ndimage

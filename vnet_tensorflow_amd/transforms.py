@@ -443,6 +443,37 @@ def plan_tail(transforms):
     return TailPlan(crop, flip, noise)
 
 
+class DeformedTailPlan(TailPlan):
+    """What plan_deformed_tail recognised: a BSplineDeformation, then the tail of a TailPlan."""
+
+    def __init__(self, deform, crop, flip, noise):
+        TailPlan.__init__(self, crop, flip, noise)
+        self.deform = deform
+
+    def draw(self, shape, rng, deformed):
+        """(coefficients, start index, flip mask, sigma, noise seed) of one sample, drawn from `rng` in the order the transforms would:
+        BSplineDeformation's rng.random(6591) * randomness, then TailPlan.draw -- the crop's draws, the flip's coin, the one noise seed.
+        The crop decides on the DEFORMED label, which exists only once the coefficients do: deformed(coef) -> (table, count), the two
+        callables of TailPlan.draw, answering for the label map deformed by `coef`."""
+        from .deform import PARAMS
+        coef = rng.random(PARAMS) * self.deform.randomness
+        table, count = deformed(coef)
+        return (coef,) + TailPlan.draw(self, shape, rng, table, count)
+
+
+def plan_deformed_tail(transforms):
+    """DeformedTailPlan of a random tail that a device-resident case can serve THROUGH the deformation -- one BSplineDeformation, then a
+    tail plan_tail recognises (ConfidenceCrop2 | RandomCrop, then optionally RandomFlip, then optionally RandomNoise) and nothing else --
+    or None.  (plan_tail keeps answering None for such a list: the dataset asks it first, then this planner.)"""
+    tf = list(transforms)
+    if not tf or type(tf[0]) is not BSplineDeformation:
+        return None
+    rest = plan_tail(tf[1:])
+    if rest is None:
+        return None
+    return DeformedTailPlan(tf[0], rest.crop, rest.flip, rest.noise)
+
+
 def run_pipeline(transforms, sample, rng):
     """The sample after every transform, its voxel spacing under 'spacing' ((1, 1, 1) when the sample came without): the spacing is
     carried past the transforms that return image and label alone (they keep the grid's spacing: crops and Padding keep origin-side
