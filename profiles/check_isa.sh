@@ -9,6 +9,8 @@ isa() { /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-fun
 for f in conv_mfma conv_x3 conv_b16 conv2_b16 elementwise input_block pool components sample prepare score summary deform; do isa $f; done
 # the fused sample-through-deformation unit: no scratch and no spills are expected of it (it reads "ok" below)
 for f in deform_sample; do isa $f; done
+# the bounding-box unit (csrc/vnet_bbox.h): read for spills and scratch only
+for f in bbox; do isa $f; done
 wait
 python3 - "$TMP" > "$OUT" <<'PY'
 import glob, os, re, subprocess, sys

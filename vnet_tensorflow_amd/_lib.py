@@ -1,6 +1,7 @@
 """ctypes binding of libvnet_hip.so (include/vnet_hip.h, include/vnet_hip_unet.h, include/vnet_hip_head.h,
 include/vnet_hip_resample.h, include/vnet_hip_components.h, include/vnet_hip_deform.h, include/vnet_hip_sample.h,
-include/vnet_hip_prepare.h, include/vnet_hip_score.h, include/vnet_hip_summary.h, include/vnet_hip_deform_sample.h).
+include/vnet_hip_prepare.h, include/vnet_hip_score.h, include/vnet_hip_summary.h, include/vnet_hip_deform_sample.h; and the package's
+own entry points of csrc/vnet_bbox.h).
 
 The library is the product: there is NO fallback.  If the shared object is missing, or a
 kernel reports an error, this module raises -- nothing silently routes to PyTorch or the CPU.
@@ -201,6 +202,16 @@ SIGNATURES_DEFORM_SAMPLE = {
     "vnet_deform_sample_patch": (_i, [_vp] * 5 + [_i] * 4 + [_d] * 3 + [_i] * 7 + [_f, _u64, _vp]),
 }
 
+# csrc/vnet_bbox.h: the package's own entry points, not part of the published C ABI (the bounding-box tool: slice stacks, components
+# inside a slice, the rendered slices), same library
+SIGNATURES_BBOX = {
+    "vnet_slice_stack_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "vnet_slice_stack_i32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "vnet_plane_cc_table_ws_bytes": (_sz, [_i, _i, _i]),
+    "vnet_plane_cc_table": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "vnet_bbox_render": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp]),
+}
+
 
 class WgradJob(ctypes.Structure):
     """include/vnet_hip.h: vnet_wgrad_job (one layer of vnet_conv_wgrad_b16_group)."""
@@ -260,11 +271,12 @@ def lib():
                 setattr(L, name, _memo(fn))    # pure size queries, asked before every launch: answer repeats from a dict
         for name, (res, args) in list(SIGNATURES_UNET.items()) + list(SIGNATURES_HEAD.items()) + list(SIGNATURES_RESAMPLE.items()) + \
                 list(SIGNATURES_COMPONENTS.items()) + list(SIGNATURES_DEFORM.items()) + list(SIGNATURES_SAMPLE.items()) + list(SIGNATURES_PREPARE.items()) + \
-                list(SIGNATURES_SCORE.items()) + list(SIGNATURES_SUMMARY.items()) + list(SIGNATURES_DEFORM_SAMPLE.items()):
+                list(SIGNATURES_SCORE.items()) + list(SIGNATURES_SUMMARY.items()) + list(SIGNATURES_DEFORM_SAMPLE.items()) + \
+                list(SIGNATURES_BBOX.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
             if name in ("vnet_bn_head_ok", "vnet_bn_head_stats_rows", "vnet_bn_head_ws_bytes", "vnet_cc_ws_bytes", "vnet_cc_table_ws_bytes",
-                        "vnet_channel_stats_ws_bytes", "vnet_cc_shape_ws_bytes"):
+                        "vnet_channel_stats_ws_bytes", "vnet_cc_shape_ws_bytes", "vnet_plane_cc_table_ws_bytes"):
                 setattr(L, name, _memo(fn))
         _lib = L
     return _lib

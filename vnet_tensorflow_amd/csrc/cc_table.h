@@ -1,4 +1,4 @@
-// cc_table.h -- the dense component table, shared by sample.hip (vnet_cc_table) and score.hip (vnet_cc_shape): the representative map of
+// cc_table.h -- the dense component table, shared by sample.hip (vnet_cc_table), score.hip (vnet_cc_shape) and bbox.hip: the representative map of
 // components.hip -> rows {representative, count, lo[3], hi[3]} in ascending representative order, and with SUMS the int64 index sums
 // {sum x, sum y, sum z} of every row.  The rank of a root (the number of roots with a smaller index) is a device-wide prefix sum,
 // written as three launches so that NO thread waits for another (no look-back, no flags, no spin):
@@ -221,6 +221,27 @@ __global__ void __launch_bounds__(SP_BLOCK) table_box_kernel(TableP p) {
 
 inline size_t cc_table_bytes(size_t n) { return 8 * n + sizeof(int) * SP_MAXBLK; }
 
+// Carves `ws` (cc_table_bytes(n), 8-byte aligned) into the block counts, the representative map and the counts, and sets the chunking
+// of p for a volume [., Y, Z] of n voxels.  Returns the representative map for the labelling passes to fill (with p.sizes).
+inline int* cc_table_carve(TableP& p, void* ws, size_t n, int* n_out, int* table, long long* sums, int max_components, int Y, int Z) {
+    p.blk = static_cast<int*>(ws);                   // (in front: the voxel arrays behind it stay 8-byte aligned whatever n is)
+    int* roots = p.blk + SP_MAXBLK;
+    p.roots = roots; p.sizes = roots + n; p.n = n_out; p.table = table; p.sums = sums; p.cap = max_components;
+    p.nvox = n; p.Y = Y; p.Z = Z;
+    p.chunk = align_up((n + SP_MAXBLK - 1) / SP_MAXBLK, (size_t)SP_BLOCK);
+    p.nblk = (int)((n + p.chunk - 1) / p.chunk);
+    return roots;
+}
+
+// count, scan, rank, box on a representative map with its counts (p.roots, p.sizes): shared with bbox.hip, whose map stays inside slices
+template <bool SUMS>
+inline int cc_table_passes(const TableP& p, hipStream_t st) {
+    if (int e = launch<table_count_kernel>(dim3(p.nblk), dim3(SP_BLOCK), 0, st, p)) return e;
+    if (int e = launch<table_scan_kernel<SUMS>>(dim3(1), dim3(SP_BLOCK), 0, st, p)) return e;
+    if (int e = launch<table_rank_kernel<SUMS>>(dim3(p.nblk), dim3(SP_BLOCK), 0, st, p)) return e;
+    return launch<table_box_kernel<SUMS>>(dim3(sp_blocks(p.nvox)), dim3(SP_BLOCK), 0, st, p);
+}
+
 // The checks of vnet_cc_table / vnet_cc_shape (VNET_E_BADARG, VNET_E_UNSUPPORTED, VNET_E_WORKSPACE, in that order), then the launches.
 template <bool SUMS>
 inline int cc_table_run(const int* label, int* n_out, int* table, long long* sums, int max_components, int X, int Y, int Z, void* ws,
@@ -231,19 +252,10 @@ inline int cc_table_run(const int* label, int* n_out, int* table, long long* sum
     if (int e = sp_count(X, Y, Z, n)) return e;
     if ((size_t)max_components > (size_t)INT_MAX / VNET_CC_ROW) return VNET_E_UNSUPPORTED;
     if (ws_bytes < cc_table_bytes(n)) return VNET_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
     TableP p{};
-    p.blk = static_cast<int*>(ws);                   // (in front: the voxel arrays behind it stay 8-byte aligned whatever n is)
-    int* roots = p.blk + SP_MAXBLK;
-    p.roots = roots; p.sizes = roots + n; p.n = n_out; p.table = table; p.sums = sums; p.cap = max_components;
-    p.nvox = n; p.Y = Y; p.Z = Z;
-    p.chunk = align_up((n + SP_MAXBLK - 1) / SP_MAXBLK, (size_t)SP_BLOCK);
-    p.nblk = (int)((n + p.chunk - 1) / p.chunk);
+    int* roots = cc_table_carve(p, ws, n, n_out, table, sums, max_components, Y, Z);
     if (int e = vnet_cc_roots(label, roots, p.sizes, X, Y, Z, stream)) return e;
-    if (int e = launch<table_count_kernel>(dim3(p.nblk), dim3(SP_BLOCK), 0, st, p)) return e;
-    if (int e = launch<table_scan_kernel<SUMS>>(dim3(1), dim3(SP_BLOCK), 0, st, p)) return e;
-    if (int e = launch<table_rank_kernel<SUMS>>(dim3(p.nblk), dim3(SP_BLOCK), 0, st, p)) return e;
-    return launch<table_box_kernel<SUMS>>(dim3(sp_blocks(n)), dim3(SP_BLOCK), 0, st, p);
+    return cc_table_passes<SUMS>(p, (hipStream_t)stream);
 }
 
 }  // namespace

@@ -14,6 +14,7 @@
 #include <math.h>
 #include <limits.h>
 #include "common.h"
+#include "cc_union.h"
 #include "../../include/vnet_hip_components.h"
 
 namespace {
@@ -23,40 +24,7 @@ constexpr size_t CC_HEAD = 16;                       // the selection key, padde
 
 typedef unsigned long long u64;
 
-// ---- link pass: every access to parent[] is an agent-scope atomic (another workgroup may be writing the word) ----
-__device__ __forceinline__ int cc_find_agent(int* parent, int a) {
-    // bounded: a is replaced by parent[a] < a, or the loop ends (parent[a] == a: a root; anything else cannot be followed)
-    for (;;) {
-        const int p = __hip_atomic_load(parent + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned)p >= (unsigned)a) return a;
-        a = p;
-    }
-}
-
-__device__ __forceinline__ void cc_unite(int* parent, int a, int b) {
-    a = cc_find_agent(parent, a);
-    b = cc_find_agent(parent, b);
-    // bounded: every trip replaces max(a, b) by a strictly smaller index (old < a, and a root is never above its voxel) or ends
-    while (a != b) {
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(parent + a, b);    // agent-scope RMW: a, a root when read, now hangs under the smaller root b
-        if (old == a) break;                         // a still was a root: linked
-        // a had been linked under `old` meanwhile and now points at min(old, b): the sets of old and b are still to be united
-        a = cc_find_agent(parent, old);
-        b = cc_find_agent(parent, b);
-    }
-}
-
-// ---- flatten pass: no union runs in this launch, so the forest is fixed and a word holds either its parent of the launch's start or its
-// root -- both are ancestors, whichever a load sees.  Relaxed single-word atomics at wavefront scope: plain loads and stores, never torn.
-__device__ __forceinline__ int cc_find_plain(const int* parent, int a) {
-    // bounded: a is replaced by parent[a] < a, or the loop ends
-    for (;;) {
-        const int p = __hip_atomic_load(parent + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        if ((unsigned)p >= (unsigned)a) return a;
-        a = p;
-    }
-}
+// cc_find_agent / cc_unite (link pass) and cc_find_plain / cc_flatten_body (flatten pass): cc_union.h, shared with bbox.hip
 
 // In the three kernels with wave-wide votes the loop runs on the block's base index, so that all 64 lanes of a wave make every trip
 // together and lane l of a wave holds voxel (wave's first voxel) + l.
@@ -102,35 +70,7 @@ __global__ void __launch_bounds__(CC_BLOCK) cc_link_kernel(const int* __restrict
 }
 
 __global__ void __launch_bounds__(CC_BLOCK) cc_flatten_kernel(int* parent, int* sizes, size_t n) {
-    const int lane = threadIdx.x & 63;
-    int acc_root = -1, acc_n = 0;                    // wave-uniform: voxels of one root seen in consecutive trips, added once
-    for (size_t base = (size_t)blockIdx.x * CC_BLOCK; base < n; base += (size_t)gridDim.x * CC_BLOCK) {
-        const size_t idx = base + threadIdx.x;
-        int r = -1;
-        if (idx < n) {
-            const int p = __hip_atomic_load(parent + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            if (p >= 0) {
-                r = cc_find_plain(parent, (int)idx);
-                if (r != p) __hip_atomic_store(parent + idx, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            }
-        }
-        if (!sizes) continue;
-        // integer adds only; the lanes that share the first foreground lane's root add their number once, the others one each
-        const bool fg = r >= 0;
-        const u64 m = __ballot(fg);
-        if (m == 0) continue;
-        const int r0 = __shfl(r, __ffsll(m) - 1, 64);
-        const bool same = fg && r == r0;
-        const u64 ms = __ballot(same);
-        if (r0 != acc_root) {
-            if (acc_n && lane == 0) atomicAdd(sizes + acc_root, acc_n);
-            acc_root = r0;
-            acc_n = 0;
-        }
-        acc_n += __popcll(ms);
-        if (fg && !same) atomicAdd(sizes + r, 1);
-    }
-    if (sizes && acc_n && lane == 0) atomicAdd(sizes + acc_root, acc_n);
+    cc_flatten_body<CC_BLOCK>(parent, sizes, n);
 }
 
 // sizes[v] > 0 only at a representative.  More voxels win; of equal counts the smaller representative (the larger ~v).

@@ -2039,6 +2039,90 @@ def summary_slices_rainbow(softmax, out=None):
     return out
 
 
+# ---- the bounding-box tool (csrc/vnet_bbox.h, the package's own entry points; rules: vnet_tensorflow_amd/bounding_box.py) ----------
+# No autograd.  They launch on torch's current stream of the calling thread, like resample.
+def slice_stack(x, axis):
+    """float32 or int32 device tensor [X,Y,Z] -> the stack of its slices [S,V,U] along `axis` (2 axial: (Z,Y,X); 1 coronal: (Y,Z,X);
+    0 sagittal: (X,Z,Y)), bit for bit (bounding_box.stack)."""
+    axis = int(axis)
+    if axis not in (0, 1, 2):
+        raise ValueError("slice_stack: axis %d (0, 1, 2)" % axis)
+    if x.dim() != 3 or x.numel() == 0:
+        raise VnetHipError("slice_stack: takes a non-empty [X,Y,Z] tensor, got %s" % (tuple(x.shape),))
+    X, Y, Z = (int(v) for v in x.shape)
+    shape = {2: (Z, Y, X), 1: (Y, Z, X), 0: (X, Z, Y)}[axis]
+    if _meta(x):
+        return torch.empty(shape, dtype=x.dtype, device="meta")
+    _need_gpu(x, "slice_stack", any_dtype=True)
+    if x.dtype not in (torch.float32, torch.int32):
+        raise VnetHipError("slice_stack: expected float32 or int32, got %s" % (x.dtype,))
+    if x.numel() > 2 ** 31 - 1:
+        raise VnetHipError("slice_stack: %dx%dx%d has more voxels than an int32 indexes" % (X, Y, Z))
+    x = x.contiguous()
+    y = torch.empty(shape, dtype=x.dtype, device=x.device)
+    entry = "vnet_slice_stack_f32" if x.dtype == torch.float32 else "vnet_slice_stack_i32"
+    with _Timed("slice stack %dx%dx%d axis %d" % (X, Y, Z, axis), 0.0, 8.0 * x.numel()):
+        check(getattr(_lib.lib(), entry)(_ptr(x), _ptr(y), X, Y, Z, axis, _thread_stream(x.device)), entry)
+    return y
+
+
+def plane_component_table(stack, max_components=65536, ws=None):
+    """The components of an int32 device stack [S,V,U] -- maximal sets of one value > 0 inside one slice, joined through u +- 1 /
+    v +- 1 -- as (n, int32 NumPy rows [n, 8], int32 NumPy classes [n]): row k = {representative, count, lo_s, lo_v, lo_u, hi_s, hi_v,
+    hi_u} in ascending representative order (bounding_box.plane_components), classes[k] the value at its representative.  One
+    read-back; when n exceeds max_components the table is made once more with capacity n.
+    ws: a uint8 device tensor of at least vnet_plane_cc_table_ws_bytes; None = ops.workspace."""
+    S, V, U = _sample_label(stack, "plane_component_table")
+    cap = int(max_components)
+    if cap < 1:
+        raise ValueError("plane_component_table: max_components %d" % cap)
+    L = _lib.lib()
+    need = L.vnet_plane_cc_table_ws_bytes(S, V, U)
+    if need == 0:
+        raise VnetHipError("plane_component_table: %dx%dx%d has more voxels than an int32 indexes" % (S, V, U))
+    if ws is None:
+        ws = workspace(need, stack.device)
+    elif ws.numel() * ws.element_size() < need:
+        raise VnetHipError("plane_component_table: ws holds %d bytes, %d needed" % (ws.numel() * ws.element_size(), need))
+    for _ in range(2):
+        out = torch.empty(cap * CC_ROW + 1, dtype=torch.int32, device=stack.device)   # the rows, then n
+        with _Timed("plane cc table %dx%dx%d" % (S, V, U), 0.0, 4.0 * stack.numel() * 7):
+            check(L.vnet_plane_cc_table(_ptr(stack), out.data_ptr() + 4 * cap * CC_ROW, _ptr(out), cap, S, V, U, _ptr(ws), need,
+                                        _thread_stream(stack.device)), "vnet_plane_cc_table")
+        # the class of every row, gathered at the representatives (rows past n hold 0: voxel 0, dropped below): one copy brings all
+        cls = stack.reshape(-1)[out[:cap * CC_ROW].reshape(cap, CC_ROW)[:, 0].long()]
+        host = torch.cat([out, cls]).cpu().numpy()
+        n = int(host[cap * CC_ROW])
+        if n <= cap:
+            break
+        cap = n
+    return n, host[:n * CC_ROW].reshape(-1, CC_ROW).copy(), host[cap * CC_ROW + 1:cap * CC_ROW + 1 + n].copy()
+
+
+def bbox_render(image, label, boxes, first, wmin, wmax, opacity):
+    """The picture of every slice, uint8 [S,V,U,3] on the device (bounding_box.render): image float32 and label int32 stacks [S,V,U],
+    boxes int32 [nb, 5] rows {x, y, w, h, label} grouped by slice (nb 0: an empty tensor), first int32 [S + 1] offsets into them."""
+    S, V, U = _sample_label(label, "bbox_render")
+    _need_gpu(image, "bbox_render")
+    if tuple(image.shape) != (S, V, U) or not image.is_contiguous():
+        raise VnetHipError("bbox_render: image %s does not go with label %s" % (tuple(image.shape), (S, V, U)))
+    for t, shape, what in ((boxes, (int(boxes.shape[0]), 5), "boxes [nb, 5]"), (first, (S + 1,), "first [S + 1]")):
+        if t.dtype != torch.int32 or t.device != label.device or tuple(t.shape) != shape or not t.is_contiguous():
+            raise VnetHipError("bbox_render: %s is a dense int32 tensor on the label's device, got %s %s" % (what, t.dtype, tuple(t.shape)))
+    alpha = int(round(float(opacity) * 256))
+    if not 0 <= alpha <= 256:
+        raise ValueError("bbox_render: opacity %r outside [0, 1]" % (opacity,))
+    # float32 arithmetic on the host: scale = float32(255) / (float32(wmax) - float32(wmin)), each operation rounded once
+    lo, hi = (torch.tensor(float(v), dtype=torch.float32, device="cpu") for v in (wmin, wmax))
+    scale = torch.tensor(255.0, dtype=torch.float32, device="cpu") / (hi - lo)
+    rgb = torch.empty((S, V, U, 3), dtype=torch.uint8, device=label.device)
+    with _Timed("bbox render %dx%dx%d" % (S, V, U), 0.0, 11.0 * label.numel()):
+        check(_lib.lib().vnet_bbox_render(_ptr(image), _ptr(label), _ptr(boxes) if boxes.numel() else None, _ptr(first), _ptr(rgb),
+                                          S, V, U, float(lo), float(hi), float(scale), alpha, _thread_stream(label.device)),
+              "vnet_bbox_render")
+    return rgb
+
+
 # ---- a case of evaluate on the device (include/vnet_hip_prepare.h; rules: vnet_tensorflow_amd/prepare.py) -------------------------
 # No autograd.  They launch on torch's current stream of the calling thread, like resample.
 STATS_MAX_BLOCKS = 1024    # VNET_STATS_MAX_BLOCKS: a channel's voxels are spread over at most this many blocks of 256 threads
