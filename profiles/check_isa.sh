@@ -6,7 +6,7 @@ cd "$(dirname "$0")/../vnet_tensorflow_amd/csrc"
 OUT=${1:-../../profiles/r06_check_isa.txt}
 TMP=$(mktemp -d)
 isa() { /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-function -Wno-unused-result -S --cuda-device-only $1.hip -o $TMP/$1.s 2>/dev/null & }
-for f in conv_mfma conv_x3 conv_b16 conv2_b16 elementwise input_block pool components sample prepare score summary deform; do isa $f; done
+for f in conv_mfma conv_x3 conv_b16 conv2_b16 elementwise input_block pool resample components sample prepare score summary deform; do isa $f; done
 # the fused sample-through-deformation unit: no scratch and no spills are expected of it (it reads "ok" below)
 for f in deform_sample; do isa $f; done
 # the bounding-box unit (csrc/vnet_bbox.h): read for spills and scratch only

@@ -210,6 +210,15 @@ def pointer_entry_points(path=None):
     return {n: ps for n, ps in header_functions(path).items() if any(_is_buffer(p) for p in ps)}
 
 
+def abi_pointer_table():
+    """pointer_entry_points() of every header the library binds (_lib.HEADERS), merged: what RecordingLib checks calls against."""
+    from vnet_tensorflow_amd import _lib
+    table = {}
+    for header, _sigs in _lib.HEADERS:
+        table.update(pointer_entry_points(os.path.join(ROOT, header)))
+    return table
+
+
 # HOST pointers of the ABI (not device buffers): the job array of the grouped filter gradient, the two result ints of vnet_packed_dims
 HOST_POINTERS = {("vnet_conv_wgrad_b16_group", "jobs"), ("vnet_packed_dims", "CQ"), ("vnet_packed_dims", "NP")}
 
@@ -218,7 +227,7 @@ class RecordingLib(object):
     """Stands in for _lib.lib(): records every entry point called and requires every device pointer to lie inside the arena."""
 
     def __init__(self, real, arena, calls):
-        self.__dict__.update(_real=real, _arena=arena, _calls=calls, _table=pointer_entry_points())
+        self.__dict__.update(_real=real, _arena=arena, _calls=calls, _table=abi_pointer_table())
 
     def __getattr__(self, name):
         fn = getattr(self._real, name)
@@ -328,7 +337,8 @@ class Guarded(object):
 def guarded(arena, modules=(), g_modules=()):
     """Inside: `torch` of `modules` allocates from the arena, `g` of `g_modules` makes arena inputs, ops.workspace hands out arena
     scratch of exactly the requested size, and _lib.lib() records calls and refuses device pointers outside the arena."""
-    from vnet_tensorflow_amd import _lib, ops
+    # (model binds _lib.lib by name when it is imported: a first import inside the context would keep this context's stand-in for good)
+    from vnet_tensorflow_amd import _lib, model, ops  # noqa: F401
     h = Guarded(arena)
     proxy = TorchProxy(arena)
     saved = []
@@ -353,3 +363,37 @@ def guarded(arena, modules=(), g_modules=()):
     finally:
         for obj, name, value in reversed(saved):
             setattr(obj, name, value)
+
+
+# ---- the body every tests/test_hip_*_guard.py shares ----------------------------------------------------------------------------
+def written_if_returned(arena, ret):
+    """`written` of run_case for cases that say themselves whether an all-0xFF output element can be a written value: check if true."""
+    if ret:
+        arena.check_written()
+
+
+def run_case(fn, dev, poison, capacity=None, written=None):
+    """fn(h) inside a guarded arena pre-filled with `poison`; guards and inputs checked, and on the 0xFF pre-fill every output element
+    written: arena.check_written(), or written(arena, what fn returned).  -> (snapshot, entry points called)"""
+    arena = Arena(dev, poison=poison) if capacity is None else Arena(dev, capacity=capacity, poison=poison)
+    with guarded(arena) as h:
+        ret = fn(h)
+        arena.check()
+        if poison == GUARD:
+            if written is None:
+                arena.check_written()
+            else:
+                written(arena, ret)
+    return arena.snapshot(), h.calls
+
+
+def check_case(cases, cid, dev, capacity=None, written=None, need_output=True):
+    """cases[cid] = (entry points the case must reach, fn): run on 0xFF, then on 0x00, and require the same bits."""
+    entries, fn = cases[cid]
+    snap_ff, calls = run_case(fn, dev, GUARD, capacity, written)
+    missing = set(entries) - set(calls)
+    assert not missing, "%s never reached %s (called: %s)" % (cid, sorted(missing), sorted(set(calls)))
+    if need_output:
+        assert snap_ff, "no output was carved from the arena"
+    snap_00, _ = run_case(fn, dev, 0x00, capacity, written)
+    assert_same_bits(snap_ff, snap_00)

@@ -55,9 +55,7 @@ def recording(env, sync=False):
     from vnet_tensorflow_amd import _lib, ops
     real_lib = _lib.lib
     real = real_lib()
-    sigs = dict(_lib.SIGNATURES)
-    sigs.update(_lib.SIGNATURES_UNET)
-    sigs.update(_lib.SIGNATURES_HEAD)
+    sigs = _lib.all_signatures()
 
     class Rec(object):
         def __getattr__(self, name):

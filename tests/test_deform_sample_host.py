@@ -19,7 +19,6 @@ from vnet_tensorflow_amd import transforms as T
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 HEADER = os.path.join(ROOT, "include", "vnet_hip_deform_sample.h")
-NAMES = {"vnet_deform_sample_patch"}
 SHAPE, SPACING = (21, 18, 23), (1.0, 0.8, 1.25)
 
 
@@ -332,44 +331,15 @@ def test_error_codes_need_no_device():
 
 # ---- the ledger of include/vnet_hip_deform_sample.h ---------------------------------------------------------------------------------------
 def test_deform_sample_header_ledger():
-    """The function is bound in _lib.SIGNATURES_DEFORM_SAMPLE with the arguments it declares (pointers, doubles, the float, the 64-bit seed)
-    and exported; it ends in `stream` and is run by a guarded case of tests/test_hip_deform_sample_guard.py; nothing of the other ten
-    headers is declared again; the Makefile compiles deform_sample.hip and rebuilds on a change of the header or of the two shared device
-    headers, which deform.hip and sample.hip include instead of holding copies; the ISA check compiles the translation unit."""
+    """include/vnet_hip_deform_sample.h beyond tests/test_abi_ledger.py: the 22 parameters begin with three inputs and two outputs under
+    these names; deform.hip and sample.hip include the two shared device headers instead of holding copies; the loaded library carries
+    the table's argument types."""
     from vnet_tensorflow_amd import _lib
-    from tests import test_hip_deform_sample_guard as TG
-    fns = guard.header_functions(HEADER)
-    assert set(fns) == set(_lib.SIGNATURES_DEFORM_SAMPLE) == NAMES
-    others = ("vnet_hip.h", "vnet_hip_unet.h", "vnet_hip_head.h", "vnet_hip_resample.h", "vnet_hip_components.h", "vnet_hip_deform.h",
-              "vnet_hip_sample.h", "vnet_hip_prepare.h", "vnet_hip_score.h", "vnet_hip_summary.h")
-    assert sorted(others + ("vnet_hip_deform_sample.h",)) == sorted(os.listdir(os.path.join(ROOT, "include")))
-    for other in others:
-        assert not set(fns) & set(guard.header_functions(os.path.join(ROOT, "include", other))), other
-    tables = (_lib.SIGNATURES, _lib.SIGNATURES_UNET, _lib.SIGNATURES_HEAD, _lib.SIGNATURES_RESAMPLE, _lib.SIGNATURES_COMPONENTS,
-              _lib.SIGNATURES_DEFORM, _lib.SIGNATURES_SAMPLE, _lib.SIGNATURES_PREPARE, _lib.SIGNATURES_SCORE, _lib.SIGNATURES_SUMMARY)
-    assert not any(set(fns) & set(t) for t in tables)
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    for name, params in fns.items():
-        assert hasattr(L, name), name
-        args = _lib.SIGNATURES_DEFORM_SAMPLE[name][1]
-        assert len(args) == len(params) == 22, name
-        assert params[-1][0] == "stream"
-        assert [a is ctypes.c_void_p for a in args] == [p[1] for p in params], name
-        assert [a is ctypes.c_double for a in args] == [p[3] == "double" for p in params], name
-        assert [a is ctypes.c_float for a in args] == [p[3] == "float" for p in params], name
-        assert [a in (ctypes.c_size_t, ctypes.c_uint64) for a in args] == [p[3] == "unsigned long long" for p in params], name
-        assert [p[0] for p in params][:5] == ["image", "deformed_label", "coef", "out_image", "out_label"]
-        assert [p[2] for p in params][:5] == [True, True, True, False, False]
-    pointer = guard.pointer_entry_points(HEADER)
-    assert set(pointer) == NAMES
-    covered = set()
-    for entries, _fn in TG.CASES.values():
-        covered |= set(entries)
-    assert set(pointer) <= covered
+    (params,) = guard.header_functions(HEADER).values()
+    assert len(params) == 22
+    assert [p[0] for p in params][:5] == ["image", "deformed_label", "coef", "out_image", "out_label"]
+    assert [p[2] for p in params][:5] == [True, True, True, False, False]
     csrc = os.path.join(ROOT, "vnet_tensorflow_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    assert "../../include/vnet_hip_deform_sample.h" in mk and " deform_sample.hip" in mk and " bspline_field.h" in mk and " philox_noise.h" in mk
-    assert " deform_sample;" in open(os.path.join(ROOT, "profiles", "check_isa.sh")).read()
     # shared, not copied: each device function is defined once, in the header its two users include
     src = {n: open(os.path.join(csrc, n)).read() for n in ("deform.hip", "sample.hip", "deform_sample.hip", "bspline_field.h", "philox_noise.h")}
     for fn_name, home in (("bs_axis(int", "bspline_field.h"), ("df_axis(double", "bspline_field.h"), ("df_lerp(double", "bspline_field.h"),

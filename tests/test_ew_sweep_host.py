@@ -267,9 +267,7 @@ def test_launches_match_the_binding(monkeypatch):
     called; the outputs have the oracle's names and sizes."""
     from vnet_tensorflow_amd import _lib
     from tests import test_hip_ew_sweep as T
-    sigs = dict(_lib.SIGNATURES)
-    sigs.update(_lib.SIGNATURES_HEAD)
-    stand = _StandIn(_lib.lib(), sigs)
+    stand = _StandIn(_lib.lib(), _lib.all_signatures())
     monkeypatch.setattr(_lib, "lib", lambda: stand)
     for name, row in S.ROWS.items():
         called = set()

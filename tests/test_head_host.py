@@ -1,6 +1,5 @@
 """No-GPU checks of the third public header, include/vnet_hip_head.h (the decoder's last batch-norm with the 1x1x1 head folded in):
 its ledger, and the variable names and order of a network built with the fused head."""
-import ctypes
 import os
 
 import numpy as np
@@ -13,27 +12,10 @@ HEAD_HEADER = os.path.join(ROOT, "include", "vnet_hip_head.h")
 
 
 def test_head_header_ledger():
-    """include/vnet_hip_head.h: every function is bound in _lib.SIGNATURES_HEAD with as many arguments as it declares and exported;
-    every one with a buffer pointer ends in `stream` and is run by a guarded case of tests/test_hip_head_guard.py; nothing of the
-    other two headers is declared again; the Makefile rebuilds on a change of it."""
-    from vnet_tensorflow_amd import _lib
+    """include/vnet_hip_head.h beyond tests/test_abi_ledger.py: the entry points that take buffers are the three every guarded case
+    of tests/test_hip_head_guard.py must reach."""
     from tests import test_hip_head_guard as TG
-    fns = guard.header_functions(HEAD_HEADER)
-    assert fns and set(fns) == set(_lib.SIGNATURES_HEAD)
-    assert not set(fns) & set(guard.header_functions())
-    assert not set(fns) & set(guard.header_functions(os.path.join(ROOT, "include", "vnet_hip_unet.h")))
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    for name, params in fns.items():
-        assert hasattr(L, name), name
-        assert len(_lib.SIGNATURES_HEAD[name][1]) == len(params), name
-    pointer = guard.pointer_entry_points(HEAD_HEADER)
-    assert set(pointer) == set(TG.FUSED)
-    assert all(params[-1][0] == "stream" for params in pointer.values())
-    covered = set()
-    for entries, _fn in TG.CASES.values():
-        covered |= set(entries)
-    assert set(pointer) <= covered
-    assert "../../include/vnet_hip_head.h" in open(os.path.join(ROOT, "vnet_tensorflow_amd", "csrc", "Makefile")).read()
+    assert set(guard.pointer_entry_points(HEAD_HEADER)) == set(TG.FUSED)
 
 
 def test_fused_head_creates_the_same_variables():

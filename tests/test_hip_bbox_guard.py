@@ -1,4 +1,4 @@
-"""-m gpu: guard bands (tests/guard.py, unchanged) around the pointer-taking entry points of csrc/vnet_bbox.h, called the way the
+"""-m gpu: guard bands (tests/guard.py) around the pointer-taking entry points of csrc/vnet_bbox.h, called the way the
 product calls them (ops.slice_stack / ops.plane_component_table / ops.bbox_render inside guarded(): inputs, outputs and scratch are
 carved from the arena).  Checked: (a) every guard byte intact and no input modified, (b) every output byte written, (c) results
 against the NumPy rules (vnet_tensorflow_amd/bounding_box.py), (d) scratch of exactly the queried size, (e) bit-identical results on a
@@ -7,9 +7,7 @@ On (b): an output element may legitimately be all 0xFF, which arena.check_writte
 their inputs off it (finite floats, labels >= 0) and the table holds no -1, so they run check_written(); a rendered byte is 255 wherever
 the grey saturates or a colour channel is full, so the render cases rest on (c) under BOTH pre-fills -- a byte the kernel skipped
 would hold 0xFF in one run and 0x00 in the other and cannot equal the rule twice.
-CASES (entry points a case must reach, function) is what the ledger test in tests/test_bbox_host.py reads."""
-import os
-
+CASES (entry points a case must reach, function) is what the ledger test in tests/test_abi_ledger.py reads."""
 import numpy as np
 import pytest
 import torch
@@ -17,7 +15,6 @@ import torch
 from tests import guard
 
 pytestmark = pytest.mark.gpu
-HEADER = os.path.join(guard.ROOT, "vnet_tensorflow_amd", "csrc", "vnet_bbox.h")
 SMALL, RAGGED, ONE = (5, 7, 9), (33, 65, 17), (1, 1, 1)
 
 
@@ -75,26 +72,6 @@ for _name, _shape in (("5x7x9", SMALL), ("33x65x17", RAGGED), ("1x1x1", ONE)):
     CASES["render " + _name] = (_R, _render(_shape))
 
 
-def _run(cid, dev, poison):
-    from vnet_tensorflow_amd import _lib
-    entries, fn = CASES[cid]
-    arena = guard.Arena(dev, capacity=64 << 20, poison=poison)
-    with guard.guarded(arena) as h:
-        # the recording library reads vnet_hip.h: teach it this header's entry points too
-        _lib.lib().__dict__["_table"].update(guard.pointer_entry_points(HEADER))
-        written_check = fn(h)
-        arena.check()
-        if poison == guard.GUARD and written_check:
-            arena.check_written()
-    return arena.snapshot(), h.calls
-
-
 @pytest.mark.parametrize("cid", sorted(CASES))
 def test_bbox_guard_bands(dev, cid):
-    entries, _ = CASES[cid]
-    snap_ff, calls = _run(cid, dev, guard.GUARD)
-    missing = set(entries) - set(calls)
-    assert not missing, "%s never reached %s (called: %s)" % (cid, sorted(missing), sorted(set(calls)))
-    assert snap_ff, "no output was carved from the arena"
-    snap_00, _ = _run(cid, dev, 0x00)
-    guard.assert_same_bits(snap_ff, snap_00)
+    guard.check_case(CASES, cid, dev, capacity=64 << 20, written=guard.written_if_returned)

@@ -1,13 +1,11 @@
-"""-m gpu: guard bands (tests/guard.py, unchanged) around the entry points of include/vnet_hip_components.h, called the way the product
+"""-m gpu: guard bands (tests/guard.py) around the entry points of include/vnet_hip_components.h, called the way the product
 calls them (ops.component_roots / largest_component / volume_threshold inside guarded(): the label, the outputs and the scratch -- of
 EXACTLY the queried size -- are all carved from the arena).  Checked: (a) every guard byte intact and no input modified, (b) every
 output element written on the 0xFF pre-fill, (c) results against the host, exactly, (d) bit-identical results on a 0xFF and a 0x00
 pre-fill.  The representative map holds -1 on the background by contract, which guard.unwritten() cannot tell from the 0xFF poison: for
 it the elements still reading 0xFF must be exactly the background voxels (the 0x00 run, where an unwritten background voxel would read
 0 and not -1, closes the argument through (c) and (d)).  CASES (entry points a case must reach, function) is what the ledger test in
-tests/test_components_host.py reads."""
-import os
-
+tests/test_abi_ledger.py reads."""
 import numpy as np
 import pytest
 import torch
@@ -15,7 +13,6 @@ import torch
 from tests import guard
 
 pytestmark = pytest.mark.gpu
-HEADER = os.path.join(guard.ROOT, "include", "vnet_hip_components.h")
 SHAPES = ((5, 4, 3), (9, 9, 9))
 
 
@@ -92,26 +89,6 @@ def _check_written(arena, minus_one):
         raise guard.GuardError("\n".join(bad))
 
 
-def _run(cid, dev, poison):
-    from vnet_tensorflow_amd import _lib
-    entries, fn = CASES[cid]
-    arena = guard.Arena(dev, capacity=32 << 20, poison=poison)
-    with guard.guarded(arena) as h:
-        # the recording library reads vnet_hip.h: teach it this header's entry points too
-        _lib.lib().__dict__["_table"].update(guard.pointer_entry_points(HEADER))
-        minus_one = fn(h)
-        arena.check()
-        if poison == guard.GUARD:
-            _check_written(arena, minus_one)
-    return arena.snapshot(), h.calls
-
-
 @pytest.mark.parametrize("cid", sorted(CASES))
 def test_components_guard_bands(dev, cid):
-    entries, _ = CASES[cid]
-    snap_ff, calls = _run(cid, dev, guard.GUARD)
-    missing = set(entries) - set(calls)
-    assert not missing, "%s never reached %s (called: %s)" % (cid, sorted(missing), sorted(set(calls)))
-    assert snap_ff, "no output was carved from the arena"
-    snap_00, _ = _run(cid, dev, 0x00)
-    guard.assert_same_bits(snap_ff, snap_00)
+    guard.check_case(CASES, cid, dev, capacity=32 << 20, written=_check_written)

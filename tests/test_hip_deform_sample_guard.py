@@ -1,12 +1,10 @@
-"""-m gpu: guard bands (tests/guard.py, unchanged) around the entry point of include/vnet_hip_deform_sample.h, called the way the product
+"""-m gpu: guard bands (tests/guard.py) around the entry point of include/vnet_hip_deform_sample.h, called the way the product
 calls it (ops.bspline_deform of the label, then ops.deform_sample_patch, inside guarded(): the case, the coefficient table, the deformed
 label and both slots are all carved from the arena).  Checked: (a) every guard byte intact and no input modified -- the gather reads the
 resident image wherever a voxel's source position falls, never past it --, (b) every element of both slots written on the 0xFF pre-fill
 (NaN / -1 poison): the zeros of the samples that leave the volume come from the kernel, (c) results against the windowed restatement
 (vnet_tensorflow_amd/sample.py: deform_patch), (d) bit-identical results on a 0xFF and a 0x00 pre-fill.  CASES (entry points a case must
-reach, function) is what the ledger test in tests/test_deform_sample_host.py reads."""
-import os
-
+reach, function) is what the ledger test in tests/test_abi_ledger.py reads."""
 import numpy as np
 import pytest
 import torch
@@ -14,7 +12,6 @@ import torch
 from tests import guard
 
 pytestmark = pytest.mark.gpu
-HEADERS = [os.path.join(guard.ROOT, "include", h) for h in ("vnet_hip_deform.h", "vnet_hip_deform_sample.h")]
 SHAPE, SPACING, PATCH = (21, 18, 23), (1.0, 0.8, 1.25), (8, 6, 10)
 SEED = 0xC0FFEE123456789
 
@@ -58,27 +55,6 @@ CASES = {
 }
 
 
-def _run(cid, dev, poison):
-    from vnet_tensorflow_amd import _lib
-    entries, fn = CASES[cid]
-    arena = guard.Arena(dev, capacity=32 << 20, poison=poison)
-    with guard.guarded(arena) as h:
-        # the recording library reads vnet_hip.h: teach it the entry points of these two headers too
-        for header in HEADERS:
-            _lib.lib().__dict__["_table"].update(guard.pointer_entry_points(header))
-        fn(h)
-        arena.check()
-        if poison == guard.GUARD:
-            arena.check_written()
-    return arena.snapshot(), h.calls
-
-
 @pytest.mark.parametrize("cid", sorted(CASES))
 def test_deform_sample_guard_bands(dev, cid):
-    entries, _ = CASES[cid]
-    snap_ff, calls = _run(cid, dev, guard.GUARD)
-    missing = set(entries) - set(calls)
-    assert not missing, "%s never reached %s (called: %s)" % (cid, sorted(missing), sorted(set(calls)))
-    assert snap_ff, "no output was carved from the arena"
-    snap_00, _ = _run(cid, dev, 0x00)
-    guard.assert_same_bits(snap_ff, snap_00)
+    guard.check_case(CASES, cid, dev, capacity=32 << 20)

@@ -1,11 +1,9 @@
-"""-m gpu: guard bands (tests/guard.py, unchanged) around the entry points of include/vnet_hip_head.h, reached the way the network
+"""-m gpu: guard bands (tests/guard.py) around the entry points of include/vnet_hip_head.h, reached the way the network
 reaches them (ops.bn_head through autograd, with and without the optional statistics rows) and directly with y stored.  Every tensor of a launch is carved from a guarded arena,
 scratch has exactly the queried size; checked: (a) every guard byte intact and no input modified, (b) every output byte written on
 the 0xFF pre-fill -- the statistics rows and the data gradient included -- (c) bit-identical results on a 0xFF and a 0x00 pre-fill.
 (Results against the oracle: tests/test_hip_head_fusion.py.)  CASES (entry points a case must reach, function) is what the ledger
-test in tests/test_head_host.py reads."""
-import os
-
+test in tests/test_abi_ledger.py reads."""
 import numpy as np
 import pytest
 import torch
@@ -13,7 +11,6 @@ import torch
 from tests import guard
 
 pytestmark = pytest.mark.gpu
-HEAD_HEADER = os.path.join(guard.ROOT, "include", "vnet_hip_head.h")
 FUSED = ("vnet_bn_act_head_fwd", "vnet_bn_act_bwd_reduce_head", "vnet_bn_act_bwd_apply_head")
 
 
@@ -95,25 +92,6 @@ CASES = {
 }
 
 
-def _run(cid, dev, poison):
-    from vnet_tensorflow_amd import _lib
-    entries, fn = CASES[cid]
-    arena = guard.Arena(dev, poison=poison)
-    with guard.guarded(arena) as h:
-        # the recording library reads vnet_hip.h: teach it this header's entry points too
-        _lib.lib().__dict__["_table"].update(guard.pointer_entry_points(HEAD_HEADER))
-        fn(h)
-        arena.check()
-        if poison == guard.GUARD:
-            arena.check_written()
-    return arena.snapshot(), h.calls
-
-
 @pytest.mark.parametrize("cid", sorted(CASES))
 def test_head_guard_bands(dev, cid):
-    entries, _ = CASES[cid]
-    snap_ff, calls = _run(cid, dev, guard.GUARD)
-    missing = set(entries) - set(calls)
-    assert not missing, "%s never reached %s (called: %s)" % (cid, sorted(missing), sorted(set(calls)))
-    snap_00, _ = _run(cid, dev, 0x00)
-    guard.assert_same_bits(snap_ff, snap_00)
+    guard.check_case(CASES, cid, dev, need_output=False)

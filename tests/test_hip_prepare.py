@@ -10,7 +10,6 @@ carved from a guarded arena (tests/guard.py: guard bands checked after every gro
 Then the product: evaluate_single_3D on a device tensor against the same array (bit for bit), and evaluate() with
 EvaluationSetting.PrepareOnDevice false and true (byte-identical label files)."""
 import math
-import os
 
 import numpy as np
 import pytest
@@ -37,7 +36,6 @@ class _Abi(object):
         self.ctx = guard.guarded(self.arena)
         self.h = self.ctx.__enter__()
         self.L = _lib.lib()
-        self.L.__dict__["_table"].update(guard.pointer_entry_points(os.path.join(guard.ROOT, "include", "vnet_hip_prepare.h")))
         return self
 
     def __exit__(self, *exc):

@@ -1,12 +1,10 @@
-"""-m gpu: guard bands (tests/guard.py, unchanged) around the four entry points of include/vnet_hip_prepare.h, called the way the product
+"""-m gpu: guard bands (tests/guard.py) around the four entry points of include/vnet_hip_prepare.h, called the way the product
 calls them (ops.channel_stats / window_intensity / crop_window / argmax_label inside guarded(): inputs, parameter tables, outputs and
 scratch are all carved from the arena, the scratch of EXACTLY the queried size).  Checked: (a) every guard byte intact and no input
 modified, (b) every output element written on the 0xFF pre-fill -- the zero fill of a window that overhangs the volume comes from the
 kernel, not from a memset -- (c) results against the NumPy restatements (vnet_tensorflow_amd/prepare.py), (d) bit-identical results on a
 0xFF and a 0x00 pre-fill of outputs and scratch.  CASES (entry points a case must reach, function) is what the ledger test in
-tests/test_prepare_host.py reads."""
-import os
-
+tests/test_abi_ledger.py reads."""
 import numpy as np
 import pytest
 import torch
@@ -15,7 +13,6 @@ from tests import guard
 from tests import prepare_data as D
 
 pytestmark = pytest.mark.gpu
-HEADER = os.path.join(guard.ROOT, "include", "vnet_hip_prepare.h")
 VOLUME, PATCH = (19, 21, 17), (16, 12, 20)
 
 
@@ -89,26 +86,6 @@ CASES = {
 }
 
 
-def _run(cid, dev, poison):
-    from vnet_tensorflow_amd import _lib
-    entries, fn = CASES[cid]
-    arena = guard.Arena(dev, capacity=48 << 20, poison=poison)
-    with guard.guarded(arena) as h:
-        # the recording library reads vnet_hip.h: teach it this header's entry points too
-        _lib.lib().__dict__["_table"].update(guard.pointer_entry_points(HEADER))
-        fn(h)
-        arena.check()
-        if poison == guard.GUARD:
-            arena.check_written()
-    return arena.snapshot(), h.calls
-
-
 @pytest.mark.parametrize("cid", sorted(CASES))
 def test_prepare_guard_bands(dev, cid):
-    entries, _ = CASES[cid]
-    snap_ff, calls = _run(cid, dev, guard.GUARD)
-    missing = set(entries) - set(calls)
-    assert not missing, "%s never reached %s (called: %s)" % (cid, sorted(missing), sorted(set(calls)))
-    assert snap_ff, "no output was carved from the arena"
-    snap_00, _ = _run(cid, dev, 0x00)
-    guard.assert_same_bits(snap_ff, snap_00)
+    guard.check_case(CASES, cid, dev, capacity=48 << 20)

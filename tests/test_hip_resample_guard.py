@@ -1,11 +1,9 @@
-"""-m gpu: guard bands (tests/guard.py, unchanged) around the two entry points of include/vnet_hip_resample.h, called the way the product
+"""-m gpu: guard bands (tests/guard.py) around the two entry points of include/vnet_hip_resample.h, called the way the product
 calls them (ops.resample inside guarded(): inputs, the divisor and the outputs are all carved from the arena).  Checked: (a) every guard
 byte intact and no input modified, (b) every output element written on the 0xFF pre-fill -- the zeros of the samples outside the source
 come from the kernel, not from a memset -- (c) results against the fp64 restatement (vnet_tensorflow_amd/resample.py), (d) bit-identical
 results on a 0xFF and a 0x00 pre-fill.  CASES (entry points a case must reach, function) is what the ledger test in
-tests/test_resample_host.py reads."""
-import os
-
+tests/test_abi_ledger.py reads."""
 import numpy as np
 import pytest
 import torch
@@ -13,7 +11,6 @@ import torch
 from tests import guard
 
 pytestmark = pytest.mark.gpu
-HEADER = os.path.join(guard.ROOT, "include", "vnet_hip_resample.h")
 UP = (0.7 / 0.5, 1.0 / 1.3, 2.5 / 1.0)                     # output spacing / source spacing of a 5x4x3 source
 DOWN = tuple(1.0 / r for r in UP)
 
@@ -61,26 +58,6 @@ CASES = {
 }
 
 
-def _run(cid, dev, poison):
-    from vnet_tensorflow_amd import _lib
-    entries, fn = CASES[cid]
-    arena = guard.Arena(dev, capacity=32 << 20, poison=poison)
-    with guard.guarded(arena) as h:
-        # the recording library reads vnet_hip.h: teach it this header's entry points too
-        _lib.lib().__dict__["_table"].update(guard.pointer_entry_points(HEADER))
-        fn(h)
-        arena.check()
-        if poison == guard.GUARD:
-            arena.check_written()
-    return arena.snapshot(), h.calls
-
-
 @pytest.mark.parametrize("cid", sorted(CASES))
 def test_resample_guard_bands(dev, cid):
-    entries, _ = CASES[cid]
-    snap_ff, calls = _run(cid, dev, guard.GUARD)
-    missing = set(entries) - set(calls)
-    assert not missing, "%s never reached %s (called: %s)" % (cid, sorted(missing), sorted(set(calls)))
-    assert snap_ff, "no output was carved from the arena"
-    snap_00, _ = _run(cid, dev, 0x00)
-    guard.assert_same_bits(snap_ff, snap_00)
+    guard.check_case(CASES, cid, dev, capacity=32 << 20)

@@ -1,4 +1,4 @@
-"""-m gpu: guard bands (tests/guard.py, unchanged) around the four entry points of include/vnet_hip_summary.h, called the way the product
+"""-m gpu: guard bands (tests/guard.py) around the four entry points of include/vnet_hip_summary.h, called the way the product
 calls them (ops.summary_slices_* inside guarded(): the input and the output are carved from the arena; there is no scratch).  Checked:
 (a) every guard byte intact and no input modified, (b) every output byte written, (c) results against the NumPy restatements
 (vnet_tensorflow_amd/summary.py), (d) bit-identical results on a 0xFF and a 0x00 pre-fill of the outputs.
@@ -6,9 +6,7 @@ On (b): an output byte here may legitimately be 0xFF, which arena.check_written(
 cases keep their inputs off it (values below 255; factor 63 on classes 0 .. 3) and run check_written(); a rainbow pixel always has one
 saturated channel (S = V = 1), so those cases rest on (c) under BOTH pre-fills -- a byte the kernel skipped would hold 0xFF in one run
 and 0x00 in the other and cannot equal the restatement twice.
-CASES (entry points a case must reach, function) is what the ledger test in tests/test_summary_host.py reads."""
-import os
-
+CASES (entry points a case must reach, function) is what the ledger test in tests/test_abi_ledger.py reads."""
 import numpy as np
 import pytest
 import torch
@@ -16,7 +14,6 @@ import torch
 from tests import guard
 
 pytestmark = pytest.mark.gpu
-HEADER = os.path.join(guard.ROOT, "include", "vnet_hip_summary.h")
 SMALL, RAGGED, ONE = (2, 5, 7, 3, 3), (1, 33, 17, 65, 1), (1, 1, 1, 1, 1)
 
 
@@ -62,26 +59,6 @@ for _name, _shape in (("2x5x7x3x3", SMALL), ("1x33x17x65x1", RAGGED), ("1x1x1x1x
     CASES["rainbow " + _name] = (_R, _rainbow(_shape))
 
 
-def _run(cid, dev, poison):
-    from vnet_tensorflow_amd import _lib
-    entries, fn = CASES[cid]
-    arena = guard.Arena(dev, capacity=48 << 20, poison=poison)
-    with guard.guarded(arena) as h:
-        # the recording library reads vnet_hip.h: teach it this header's entry points too
-        _lib.lib().__dict__["_table"].update(guard.pointer_entry_points(HEADER))
-        written_check = fn(h)
-        arena.check()
-        if poison == guard.GUARD and written_check:
-            arena.check_written()
-    return arena.snapshot(), h.calls
-
-
 @pytest.mark.parametrize("cid", sorted(CASES))
 def test_summary_guard_bands(dev, cid):
-    entries, _ = CASES[cid]
-    snap_ff, calls = _run(cid, dev, guard.GUARD)
-    missing = set(entries) - set(calls)
-    assert not missing, "%s never reached %s (called: %s)" % (cid, sorted(missing), sorted(set(calls)))
-    assert snap_ff, "no output was carved from the arena"
-    snap_00, _ = _run(cid, dev, 0x00)
-    guard.assert_same_bits(snap_ff, snap_00)
+    guard.check_case(CASES, cid, dev, capacity=48 << 20, written=guard.written_if_returned)

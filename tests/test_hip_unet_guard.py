@@ -1,11 +1,9 @@
-"""-m gpu: guard bands (tests/guard.py, unchanged) around the entry points the U-Net adds or opens: the two max-pooling entry
+"""-m gpu: guard bands (tests/guard.py) around the entry points the U-Net adds or opens: the two max-pooling entry
 points of include/vnet_hip_unet.h and the ks = 3 forward / statistics / accumulate / filter-gradient launches of vnet_hip.h.  Every
 tensor of a launch is carved from a guarded arena, scratch has exactly the queried size; checked: (a) every guard byte intact and no
 input modified, (b) every output byte written on the 0xFF pre-fill -- this is what catches a dx element the pooling backward left
 unwritten -- (c) results against the fp64 oracle, (d) bit-identical results on a 0xFF and a 0x00 pre-fill.
-CASES (entry points a case must reach, function) is what the ledger test in tests/test_unet_host.py reads."""
-import os
-
+CASES (entry points a case must reach, function) is what the ledger test in tests/test_abi_ledger.py reads."""
 import numpy as np
 import pytest
 import torch
@@ -15,7 +13,6 @@ from tests import guard, unet_oracle as U
 from tests.util import check_close
 
 pytestmark = pytest.mark.gpu
-UNET_HEADER = os.path.join(guard.ROOT, "include", "vnet_hip_unet.h")
 
 
 def _out(h, name, shape):
@@ -129,25 +126,6 @@ CASES = {
 }
 
 
-def _run(cid, dev, poison):
-    from vnet_tensorflow_amd import _lib
-    entries, fn = CASES[cid]
-    arena = guard.Arena(dev, poison=poison)
-    with guard.guarded(arena) as h:
-        # the recording library reads vnet_hip.h: teach it the second header's entry points too
-        _lib.lib().__dict__["_table"].update(guard.pointer_entry_points(UNET_HEADER))
-        fn(h)
-        arena.check()
-        if poison == guard.GUARD:
-            arena.check_written()
-    return arena.snapshot(), h.calls
-
-
 @pytest.mark.parametrize("cid", sorted(CASES))
 def test_unet_guard_bands(dev, cid):
-    entries, _ = CASES[cid]
-    snap_ff, calls = _run(cid, dev, guard.GUARD)
-    missing = set(entries) - set(calls)
-    assert not missing, "%s never reached %s (called: %s)" % (cid, sorted(missing), sorted(set(calls)))
-    snap_00, _ = _run(cid, dev, 0x00)
-    guard.assert_same_bits(snap_ff, snap_00)
+    guard.check_case(CASES, cid, dev, need_output=False)

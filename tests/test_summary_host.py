@@ -19,7 +19,6 @@ from vnet_tensorflow_amd import summary as S
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 HEADER = os.path.join(ROOT, "include", "vnet_hip_summary.h")
-NAMES = {"vnet_summary_slices_f32", "vnet_summary_slices_i32", "vnet_summary_slices_i64", "vnet_summary_rainbow_f32"}
 
 # float32 bit patterns of softmax values at which a fused multiply-add of 6 * H - 3 / - 2 / - 4 (one rounding instead of two) changes an
 # output byte of the rainbow rule: found on the CPU by comparing summary.rainbow with fused_rainbow below over 8 * 10^7 seeded uniform
@@ -394,39 +393,10 @@ def test_tag_rule():
 
 # ---- the ledger of include/vnet_hip_summary.h ----------------------------------------------------------------------------------------
 def test_summary_header_ledger():
-    """Every function is bound in _lib.SIGNATURES_SUMMARY with as many arguments as it declares and exported; every one takes buffer
-    pointers, ends in `stream` and is run by a guarded case of tests/test_hip_summary_guard.py; the name set is disjoint from the nine
-    other tables and headers; the Makefile compiles summary.hip and rebuilds on a change of the header; the ISA check compiles the unit."""
-    from vnet_tensorflow_amd import _lib, ops
-    from tests import test_hip_summary_guard as TG
-    fns = guard.header_functions(HEADER)
-    assert set(fns) == set(_lib.SIGNATURES_SUMMARY) == NAMES
-    others = ("vnet_hip.h", "vnet_hip_unet.h", "vnet_hip_head.h", "vnet_hip_resample.h", "vnet_hip_components.h", "vnet_hip_deform.h",
-              "vnet_hip_sample.h", "vnet_hip_prepare.h", "vnet_hip_score.h")
-    for other in others:
-        assert not set(fns) & set(guard.header_functions(os.path.join(ROOT, "include", other))), other
-    tables = (_lib.SIGNATURES, _lib.SIGNATURES_UNET, _lib.SIGNATURES_HEAD, _lib.SIGNATURES_RESAMPLE, _lib.SIGNATURES_COMPONENTS,
-              _lib.SIGNATURES_DEFORM, _lib.SIGNATURES_SAMPLE, _lib.SIGNATURES_PREPARE, _lib.SIGNATURES_SCORE)
-    for t in tables:
-        assert not set(fns) & set(t)
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    for name, params in fns.items():
-        assert hasattr(L, name), name
-        args = _lib.SIGNATURES_SUMMARY[name][1]
-        assert len(args) == len(params), name
-        assert [a is ctypes.c_void_p for a in args] == [p[1] for p in params], name
-        assert not any(p[3] in ("size_t", "long long") for p in params), name
-        assert all(a is ctypes.c_int for a, p in zip(args, params) if not p[1]), name
-    pointer = guard.pointer_entry_points(HEADER)
-    assert set(pointer) == NAMES
-    assert all(ps[-1][0] == "stream" for ps in pointer.values())
-    covered = set()
-    for entries, _fn in TG.CASES.values():
-        covered |= set(entries)
-    assert set(pointer) <= covered
-    mk = open(os.path.join(ROOT, "vnet_tensorflow_amd", "csrc", "Makefile")).read()
-    assert "../../include/vnet_hip_summary.h" in mk and " summary.hip" in mk
-    assert " summary " in open(os.path.join(ROOT, "profiles", "check_isa.sh")).read()
+    """include/vnet_hip_summary.h beyond tests/test_abi_ledger.py: no entry point takes a size or a 64-bit count; the grid cap is one
+    number in the header and in ops."""
+    from vnet_tensorflow_amd import ops
+    assert not any(p[3] in ("size_t", "long long") for params in guard.header_functions(HEADER).values() for p in params)
     assert ops.SUMMARY_MAX_BLOCKS == 4096 and "#define VNET_SUMMARY_MAX_BLOCKS 4096" in open(HEADER).read()
 
 

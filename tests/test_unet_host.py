@@ -16,12 +16,10 @@ import pytest
 import torch
 
 from oracle import vnet_oracle as O
-from tests import guard, unet_oracle as U, unet_torch as UT
+from tests import unet_oracle as U, unet_torch as UT
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 CASES = ("c1k2", "c3k3", "odd")
-UNET_HEADER = os.path.join(ROOT, "include", "vnet_hip_unet.h")
 
 
 def load_fixture(case):
@@ -188,22 +186,12 @@ def test_route_ks3():
 
 
 def test_unet_header_ledger():
-    """include/vnet_hip_unet.h: every function is bound in _lib.SIGNATURES_UNET and exported; every one with a buffer pointer is run
-    by a guarded case of tests/test_hip_unet_guard.py; nothing of vnet_hip.h is declared again."""
-    from vnet_tensorflow_amd import _lib
+    """include/vnet_hip_unet.h beyond tests/test_abi_ledger.py: the guarded cases of tests/test_hip_unet_guard.py also run the
+    ks = 3 launches of vnet_hip.h the U-Net opens."""
     from tests import test_hip_unet_guard as TG
-    fns = guard.header_functions(UNET_HEADER)
-    assert fns and set(fns) == set(_lib.SIGNATURES_UNET)
-    assert not set(fns) & set(guard.header_functions())
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    for name, params in fns.items():
-        assert hasattr(L, name), name
-        assert len(_lib.SIGNATURES_UNET[name][1]) == len(params), name
-        assert params[-1][0] == "stream"
     covered = set()
     for entries, _fn in TG.CASES.values():
         covered |= set(entries)
-    assert set(guard.pointer_entry_points(UNET_HEADER)) <= covered
     assert {"vnet_conv_fwd", "vnet_conv_fwd_stats", "vnet_conv_fwd_acc", "vnet_conv_wgrad"} <= covered
 
 

@@ -1,7 +1,4 @@
-"""ctypes binding of libvnet_hip.so (include/vnet_hip.h, include/vnet_hip_unet.h, include/vnet_hip_head.h,
-include/vnet_hip_resample.h, include/vnet_hip_components.h, include/vnet_hip_deform.h, include/vnet_hip_sample.h,
-include/vnet_hip_prepare.h, include/vnet_hip_score.h, include/vnet_hip_summary.h, include/vnet_hip_deform_sample.h; and the package's
-own entry points of csrc/vnet_bbox.h).
+"""ctypes binding of libvnet_hip.so: HEADERS below lists every header of its C ABI with the signature table that binds it.
 
 The library is the product: there is NO fallback.  If the shared object is missing, or a
 kernel reports an error, this module raises -- nothing silently routes to PyTorch or the CPU.
@@ -213,6 +210,43 @@ SIGNATURES_BBOX = {
 }
 
 
+# Every header of the library's C ABI, in the order they were published, with the table that binds it (path relative to the repository
+# root).  lib() binds them all, tests/guard.py reads the pointer parameters of all, tests/test_abi_ledger.py holds each row to its header.
+HEADERS = (
+    ("include/vnet_hip.h", SIGNATURES),
+    ("include/vnet_hip_unet.h", SIGNATURES_UNET),
+    ("include/vnet_hip_head.h", SIGNATURES_HEAD),
+    ("include/vnet_hip_resample.h", SIGNATURES_RESAMPLE),
+    ("include/vnet_hip_components.h", SIGNATURES_COMPONENTS),
+    ("include/vnet_hip_deform.h", SIGNATURES_DEFORM),
+    ("include/vnet_hip_sample.h", SIGNATURES_SAMPLE),
+    ("include/vnet_hip_prepare.h", SIGNATURES_PREPARE),
+    ("include/vnet_hip_score.h", SIGNATURES_SCORE),
+    ("include/vnet_hip_summary.h", SIGNATURES_SUMMARY),
+    ("include/vnet_hip_deform_sample.h", SIGNATURES_DEFORM_SAMPLE),
+    ("vnet_tensorflow_amd/csrc/vnet_bbox.h", SIGNATURES_BBOX),
+)
+
+
+def all_signatures():
+    """{name: (restype, argtypes)} of the whole ABI; a name two tables bind is an error."""
+    sigs = {}
+    for header, table in HEADERS:
+        twice = set(sigs) & set(table)
+        if twice:
+            raise ValueError("%s binds %s again" % (header, sorted(twice)))
+        sigs.update(table)
+    return sigs
+
+
+# Pure size queries, asked before every launch: lib() answers repeats from a dict.  (The other _ok queries read options or are asked once.)
+MEMO_EXTRAS = {"vnet_conv_stats_from_reduce", "vnet_packed_weight_floats", "vnet_bn_head_ok"}
+
+
+def memoised(name):
+    return name.endswith("_ws_bytes") or name.endswith("_stats_rows") or name in MEMO_EXTRAS
+
+
 class WgradJob(ctypes.Structure):
     """include/vnet_hip.h: vnet_wgrad_job (one layer of vnet_conv_wgrad_b16_group)."""
     _fields_ = [("x0", ctypes.c_void_p), ("x1", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("dw", ctypes.c_void_p),
@@ -262,22 +296,14 @@ def lib():
         # allocator live in ONE HIP runtime (loading ours first would bind /opt/rocm's copy instead).
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)          # AttributeError if a declared symbol is not exported
-            fn.restype, fn.argtypes = res, args
-            if name == "vnet_conv_b16_stats_rows":
-                setattr(L, name, _memo(fn, (b"BF16_DEEP", b"BF16_DEEP_TARGET"), L))     # (the kernel choice follows these options)
-            elif name.endswith("_ws_bytes") or name.endswith("_stats_rows") or name == "vnet_conv_stats_from_reduce" or name == "vnet_packed_weight_floats":
-                setattr(L, name, _memo(fn))    # pure size queries, asked before every launch: answer repeats from a dict
-        for name, (res, args) in list(SIGNATURES_UNET.items()) + list(SIGNATURES_HEAD.items()) + list(SIGNATURES_RESAMPLE.items()) + \
-                list(SIGNATURES_COMPONENTS.items()) + list(SIGNATURES_DEFORM.items()) + list(SIGNATURES_SAMPLE.items()) + list(SIGNATURES_PREPARE.items()) + \
-                list(SIGNATURES_SCORE.items()) + list(SIGNATURES_SUMMARY.items()) + list(SIGNATURES_DEFORM_SAMPLE.items()) + \
-                list(SIGNATURES_BBOX.items()):
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-            if name in ("vnet_bn_head_ok", "vnet_bn_head_stats_rows", "vnet_bn_head_ws_bytes", "vnet_cc_ws_bytes", "vnet_cc_table_ws_bytes",
-                        "vnet_channel_stats_ws_bytes", "vnet_cc_shape_ws_bytes", "vnet_plane_cc_table_ws_bytes"):
-                setattr(L, name, _memo(fn))
+        for _header, table in HEADERS:
+            for name, (res, args) in table.items():
+                fn = getattr(L, name)          # AttributeError if a declared symbol is not exported
+                fn.restype, fn.argtypes = res, args
+                if name == "vnet_conv_b16_stats_rows":
+                    setattr(L, name, _memo(fn, (b"BF16_DEEP", b"BF16_DEEP_TARGET"), L))     # (the kernel choice follows these options)
+                elif memoised(name):
+                    setattr(L, name, _memo(fn))    # pure size queries, asked before every launch: answer repeats from a dict
         _lib = L
     return _lib
 

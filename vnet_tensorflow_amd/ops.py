@@ -145,6 +145,12 @@ def _stream():
     return _raw_stream()
 
 
+def _thread_stream(device):
+    """torch's current stream of the CALLING thread on `device`, never the _LAUNCH_ON redirect: for the ops that also run on loader
+    threads, inside side_work."""
+    return torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch._C._cuda_getDevice())
+
+
 # ---- device-resident step state (include/vnet_hip.h: vnet_step_state_set) ---------------------------------
 # A captured hipGraph freezes kernel arguments; the learning rate, Adam's bias-corrected lr_t and the dropout stream
 # position live in a 32-byte device buffer that one tiny eager kernel rewrites before each replay.
@@ -1655,9 +1661,7 @@ def bspline_deform(x, coef, spacing, kind="image"):
     X, Y, Z = (int(v) for v in x.shape[:3])
     C = int(x.shape[3]) if x.dim() == 4 else 1
     y = torch.empty(tuple(x.shape), dtype=want, device=x.device)
-    # torch's current stream of THIS thread, never the redirect of the parameter-gradient section (_LAUNCH_ON is process-wide and
-    # belongs to the training step; this op also runs on loader threads, inside side_work)
-    stream = torch._C._cuda_getCurrentRawStream(x.device.index if x.device.index is not None else torch._C._cuda_getDevice())
+    stream = _thread_stream(x.device)          # (this op also runs on loader threads, inside side_work)
     entry = "vnet_bspline_deform_f32" if kind == "image" else "vnet_bspline_deform_i32"
     with _Timed("bspline_deform %s %dx%dx%d %d" % (kind, X, Y, Z, C), 0.0, 4.0 * (x.numel() + y.numel())):
         check(getattr(L, entry)(_ptr(x), _ptr(y), X, Y, Z, C, _ptr(coef), *spacing, stream), entry)
@@ -1796,10 +1800,6 @@ def volume_threshold(label, volume, spacing=(1.0, 1.0, 1.0)):
 # These run on loader threads inside side_work: they launch on torch's current stream of the CALLING thread, never on the redirect of
 # the parameter-gradient section (_LAUNCH_ON is process-wide and belongs to the training step).
 CC_ROW = 8                 # VNET_CC_ROW: representative, count, lo[3], hi[3]
-
-
-def _thread_stream(device):
-    return torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch._C._cuda_getDevice())
 
 
 def _sample_label(label, what):
