@@ -11,6 +11,8 @@ for f in conv_mfma conv_x3 conv_b16 conv2_b16 elementwise input_block pool resam
 for f in deform_sample; do isa $f; done
 # the bounding-box unit (csrc/vnet_bbox.h): read for spills and scratch only
 for f in bbox; do isa $f; done
+# the data-preparation unit (csrc/vnet_tools.h): read for spills and scratch only
+for f in morph; do isa $f; done
 wait
 python3 - "$TMP" > "$OUT" <<'PY'
 import glob, os, re, subprocess, sys

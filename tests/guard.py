@@ -219,8 +219,10 @@ def abi_pointer_table():
     return table
 
 
-# HOST pointers of the ABI (not device buffers): the job array of the grouped filter gradient, the two result ints of vnet_packed_dims
-HOST_POINTERS = {("vnet_conv_wgrad_b16_group", "jobs"), ("vnet_packed_dims", "CQ"), ("vnet_packed_dims", "NP")}
+# HOST pointers of the ABI (not device buffers): the job array of the grouped filter gradient, the two result ints of vnet_packed_dims,
+# the values of vnet_select_bits (copied into the kernel's arguments)
+HOST_POINTERS = {("vnet_conv_wgrad_b16_group", "jobs"), ("vnet_packed_dims", "CQ"), ("vnet_packed_dims", "NP"),
+                 ("vnet_select_bits", "values")}
 
 
 class RecordingLib(object):
@@ -372,11 +374,11 @@ def written_if_returned(arena, ret):
         arena.check_written()
 
 
-def run_case(fn, dev, poison, capacity=None, written=None):
+def run_case(fn, dev, poison, capacity=None, written=None, modules=()):
     """fn(h) inside a guarded arena pre-filled with `poison`; guards and inputs checked, and on the 0xFF pre-fill every output element
     written: arena.check_written(), or written(arena, what fn returned).  -> (snapshot, entry points called)"""
     arena = Arena(dev, poison=poison) if capacity is None else Arena(dev, capacity=capacity, poison=poison)
-    with guarded(arena) as h:
+    with guarded(arena, modules=modules) as h:
         ret = fn(h)
         arena.check()
         if poison == GUARD:
@@ -387,13 +389,13 @@ def run_case(fn, dev, poison, capacity=None, written=None):
     return arena.snapshot(), h.calls
 
 
-def check_case(cases, cid, dev, capacity=None, written=None, need_output=True):
+def check_case(cases, cid, dev, capacity=None, written=None, need_output=True, modules=()):
     """cases[cid] = (entry points the case must reach, fn): run on 0xFF, then on 0x00, and require the same bits."""
     entries, fn = cases[cid]
-    snap_ff, calls = run_case(fn, dev, GUARD, capacity, written)
+    snap_ff, calls = run_case(fn, dev, GUARD, capacity, written, modules)
     missing = set(entries) - set(calls)
     assert not missing, "%s never reached %s (called: %s)" % (cid, sorted(missing), sorted(set(calls)))
     if need_output:
         assert snap_ff, "no output was carved from the arena"
-    snap_00, _ = run_case(fn, dev, 0x00, capacity, written)
+    snap_00, _ = run_case(fn, dev, 0x00, capacity, written, modules)
     assert_same_bits(snap_ff, snap_00)

@@ -1,4 +1,4 @@
-"""-m gpu: the kernels of csrc/morph.hip (libvnet_tools.so) through vnet_tensorflow_amd/morph.py, every comparison `==` against the
+"""-m gpu: the kernels of csrc/morph.hip through vnet_tensorflow_amd/morph.py, every comparison `==` against the
 NumPy rules of vnet_tensorflow_amd/prepare_data.py, and the two device tools end to end on a case written to a temporary directory.
 Shapes: the smallest at which a kernel can go wrong -- one voxel, less than a word, 63 / 64 / 65 voxels per row, (19,37,130) which
 crosses the dilation's 8 x 32 tile in A and B and has three words with a ragged last one, (9,9,200) narrower than the ball of radius 8,

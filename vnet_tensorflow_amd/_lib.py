@@ -209,6 +209,15 @@ SIGNATURES_BBOX = {
     "vnet_bbox_render": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp]),
 }
 
+# csrc/vnet_tools.h: the package's own entry points as well (the data-preparation tools' bit-packed morphology, morph.py), same library
+SIGNATURES_TOOLS = {
+    "vnet_select_bits": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "vnet_dilate_bits": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "vnet_bits_bbox": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "vnet_masked_crop": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "vnet_unpack_bits": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+}
+
 
 # Every header of the library's C ABI, in the order they were published, with the table that binds it (path relative to the repository
 # root).  lib() binds them all, tests/guard.py reads the pointer parameters of all, tests/test_abi_ledger.py holds each row to its header.
@@ -225,6 +234,7 @@ HEADERS = (
     ("include/vnet_hip_summary.h", SIGNATURES_SUMMARY),
     ("include/vnet_hip_deform_sample.h", SIGNATURES_DEFORM_SAMPLE),
     ("vnet_tensorflow_amd/csrc/vnet_bbox.h", SIGNATURES_BBOX),
+    ("vnet_tensorflow_amd/csrc/vnet_tools.h", SIGNATURES_TOOLS),
 )
 
 

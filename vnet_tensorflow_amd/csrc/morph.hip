@@ -1,4 +1,4 @@
-// morph.hip -- the data-preparation tools on the device (csrc/vnet_tools.h; libvnet_tools.so), gfx950.
+// morph.hip -- the data-preparation tools on the device (csrc/vnet_tools.h), gfx950.
 //   vnet_select_bits : one wave per word: lane k reads voxel c = 64 w + k of a row in the label's own dtype, the wave's ballot is the
 //                      word (lanes at c >= C vote 0, which keeps the unused high bits zero).  Reads the label once.
 //   vnet_dilate_bits : a block takes a tile of 8 x 32 rows of ONE word column w.  It stages the (8 + 2r) x (32 + 2r) source words of

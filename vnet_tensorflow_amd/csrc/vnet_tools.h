@@ -1,6 +1,5 @@
-/* vnet_tools.h -- the entry points of libvnet_tools.so, a small library of its own beside libvnet_hip.so: the offline data-preparation
- * tools (vnet_tensorflow_amd/prepare_data.py; the reference's utils/prepare_data) on the device.  Not part of the training library's
- * C ABI under include/.  A label map becomes a bit-packed mask, the mask is dilated by ITK's ball, its bounding box is found, and a
+/* vnet_tools.h -- the package's OWN entry points of libvnet_hip.so, not part of the published C ABI under include/: what the offline
+ * data-preparation tools (vnet_tensorflow_amd/prepare_data.py; the reference's utils/prepare_data) run on the device.  A label map becomes a bit-packed mask, the mask is dilated by ITK's ball, its bounding box is found, and a
  * window of a volume is cut out with the voxels outside the mask zeroed.  The rules: prepare_data.py and DESIGN.md section 6i.
  * Every volume is a dense array [A,B,C] with C fastest; the axes carry no meaning (the ball is isotropic).
  * A PACKED MASK is an int64 array [A,B,W], W = ceil(C / 64): bit k of word w of row (a, b) is voxel c = 64 w + k.  The bits of a row's

@@ -1,6 +1,6 @@
-"""ctypes binding of libvnet_tools.so (csrc/vnet_tools.h, csrc/morph.hip) and its device ops: the bit-packed morphology the
-data-preparation tools run on the device (vnet_tensorflow_amd/prepare_data.py).  A library of its own beside
-libvnet_hip.so: offline tools, not part of the training library's C ABI, so none of this is in _lib.HEADERS.
+"""The device ops over csrc/vnet_tools.h (csrc/morph.hip): the bit-packed morphology the data-preparation tools run on the device
+(vnet_tensorflow_amd/prepare_data.py).  The header is the package's own, not part of the published C ABI; its
+entry points live in libvnet_hip.so and are bound by _lib.lib() like every other row of _lib.HEADERS.
 
 Same conventions as _lib / ops: there is NO fallback -- a missing library or a kernel that reports an error raises VnetHipError,
 nothing routes to PyTorch or the CPU; ops launch on torch's current stream of the calling thread; outputs are allocated through this
@@ -10,57 +10,22 @@ Every op takes a dense 3-D device tensor [A,B,C] and gives the axes no meaning. 
 bit k of word w is voxel c = 64 w + k, the unused high bits of a row's last word are zero.  The word count loses C, so the ops that
 take a mask take C beside it."""
 import ctypes
-import os
 
 import torch
 
-from ._lib import VnetHipError, check
+from ._lib import VnetHipError, check, lib
+from .ops import _thread_stream as _stream
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("VNET_TOOLS_LIB") or os.path.join(_HERE, "libvnet_tools.so")
-HEADER = "vnet_tensorflow_amd/csrc/vnet_tools.h"
-
-_vp, _i = ctypes.c_void_p, ctypes.c_int
-
-# name -> (restype, argtypes) : every symbol csrc/vnet_tools.h declares (tests/test_prepare_data_host.py holds the table to the header)
-SIGNATURES_TOOLS = {
-    "vnet_select_bits": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
-    "vnet_dilate_bits": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    "vnet_bits_bbox": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "vnet_masked_crop": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "vnet_unpack_bits": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-}
+HEADER = "vnet_tensorflow_amd/csrc/vnet_tools.h"          # its row of _lib.HEADERS
 
 MAX_VALUES, MAX_RADIUS, MAX_VOXELS = 16, 8, 2 ** 31 - 1
 # dtype_code of vnet_select_bits
 DTYPE_CODES = {torch.uint8: 0, torch.int8: 1, torch.int16: 2, torch.uint16: 3, torch.int32: 4}
 _RANGES = {0: (0, 255), 1: (-128, 127), 2: (-32768, 32767), 3: (0, 65535), 4: (-2 ** 31, 2 ** 31 - 1)}
 
-_tools = None
-
-
-def lib():
-    """The loaded libvnet_tools.so (raises if it has not been built: there is no fallback path)."""
-    global _tools
-    if _tools is None:
-        if not os.path.exists(LIB_PATH):
-            raise VnetHipError("libvnet_tools.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(hipcc, gfx950).  The HIP library is the only compute path." % LIB_PATH)
-        # torch (imported above) has loaded its own libamdhip64 by now: both libraries and torch's streams live in ONE HIP runtime
-        L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES_TOOLS.items():
-            fn = getattr(L, name)              # AttributeError if a declared symbol is not exported
-            fn.restype, fn.argtypes = res, args
-        _tools = L
-    return _tools
-
 
 def words(C):
     return (int(C) + 63) // 64
-
-
-def _stream(device):
-    return torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch._C._cuda_getDevice())
 
 
 def _volume(x, what):
