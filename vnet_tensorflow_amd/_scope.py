@@ -78,11 +78,19 @@ class VariableStore(object):
         return out
 
     def load_state_dict(self, sd):
+        """Every variable of the store from `sd`, or none: a table that lacks one (it would silently keep its initial value) or
+        holds an unknown one is refused before anything is written -- what tf_checkpoint.split_training_state does for the
+        reference's container."""
+        own = list(self.params) + list(self.buffers)
+        missing = [k for k in own if k not in sd]
+        if missing:
+            raise KeyError("checkpoint lacks %d of the network's %d variables, e.g. %s" % (len(missing), len(own), ", ".join(missing[:3])))
+        for k in sd:
+            if k not in self.params and k not in self.buffers:
+                raise KeyError("unknown variable %r" % k)
         with torch.no_grad():
             for k, v in sd.items():
                 dst = self.params.get(k, self.buffers.get(k))
-                if dst is None:
-                    raise KeyError("unknown variable %r" % k)
                 dst.copy_(torch.as_tensor(v).to(dst.device, dst.dtype).reshape(dst.shape))
 
 

@@ -143,11 +143,15 @@ class VolumeDataset(object):
     a multiple of world * batch and strided by rank, so the shards are disjoint and every rank yields the same number
     of batches (the gradient all-reduces of the ranks pair up one to one; a rank with fewer steps would leave the
     others blocked in RCCL).  Crop windows are drawn from a per-rank generator.  train=False (the test pass, which holds no
-    collective) is not sharded: every rank iterates all cases."""
+    collective) is not sharded: every rank iterates all cases.
+
+    The epoch rule: the plan of epoch e -- order and crop seeds, from which every window, flip, noise draw and deformation of the
+    epoch follows -- is a function of (seed, rank, world, e) alone.  A run restored at epoch e passes epoch=e (or calls
+    skip_epochs) and trains on what the uninterrupted run would have seen, not on epoch 0's samples again."""
 
     def __init__(self, data_dir, image_filenames, label_filename, classes, patch_shape, batch_size,
                  train=True, seed=0, synthetic=None, rank=0, world=1, cache=None, transforms=None,
-                 device_tail=None, device_cache_bytes=16 << 30, max_components=4096):
+                 device_tail=None, device_cache_bytes=16 << 30, max_components=4096, epoch=0):
         self.image_filenames, self.label_filename = list(image_filenames), label_filename
         self.classes, self.patch, self.batch = list(classes), tuple(patch_shape), int(batch_size)
         self.train, self.seed, self.epoch = train, int(seed), 0
@@ -207,6 +211,17 @@ class VolumeDataset(object):
         if self.train and self.steps_per_epoch() == 0:
             raise ValueError("%d cases give no full batch for %d rank(s) x batch %d: every rank needs at least one batch per "
                              "epoch (a rank without work would sit in no collective at all)" % (len(self.cases), world, self.batch))
+        # epoch = e (a run restored at epoch e, model.image2label._train): the next plan is the e-th plan of a dataset that started at 0
+        self.skip_epochs(epoch)
+
+    def skip_epochs(self, n):
+        """Stand where a dataset stands after n more epochs, without making a batch: the shuffle of an epoch is a function of
+        (seed, epoch), its crop seeds are the next steps_per_epoch() x batch draws of this rank's generator -- the very draws
+        epoch_plan() makes, consumed here in the same calls, so the plans that follow are those of the uninterrupted sequence."""
+        for _ in range(int(n)):
+            for _ in range(self.steps_per_epoch()):
+                self.rng.integers(0, 2 ** 62, size=self.batch)
+            self.epoch += 1
 
     def steps_per_epoch(self):
         # the TEST pass holds no collective (model.image2label.train: forward + metrics per rank), so it is not sharded: every

@@ -936,7 +936,8 @@ class image2label(object):
             f.write('model_checkpoint_path: "%s"\nall_model_checkpoint_paths: "%s"\n' % (base, base))
         return prefix
 
-    def _dataset(self, data_dir, train):
+    def _dataset(self, data_dir, train, epoch=0):
+        """epoch: the epoch the first plan belongs to (data.VolumeDataset's epoch rule; a restored run's start_epoch)."""
         tf = None
         if self.training_pipeline:
             # TrainingSetting.Pipeline: the reference's transform YAML (model.py:340-372); the index / intensity transforms and
@@ -954,7 +955,7 @@ class image2label(object):
             tail = {"device_tail": self.device, "device_cache_bytes": int(float(getattr(self, "device_cache_gb", 16)) * 2 ** 30)}
         return vdata.VolumeDataset(data_dir, self.image_filenames, self.label_filename, self.label_classes,
                                    self.patch_shape, self.batch_size, train=train, synthetic=self.synthetic,
-                                   rank=self.rank, world=self.world, transforms=tf, **tail)
+                                   rank=self.rank, world=self.world, transforms=tf, epoch=epoch, **tail)
 
     # -- reference model.py:632-815 ---------------------------------------------------------------------------
     @in_context
@@ -982,7 +983,9 @@ class image2label(object):
             self._print("{}: Last checkpoint epoch: {}".format(_now(), self.start_epoch))
             self._print("{}: Last checkpoint global step: {}".format(_now(), self.global_step))
         self._open_summaries()
-        train_set = self._dataset(self.train_data_dir, True)
+        # a restored run goes on with the plan of epoch start_epoch -- that epoch's shuffle and crop seeds, from its first batch (a
+        # mid-epoch checkpoint starts its epoch again, as the reference does) -- not with epoch 0's
+        train_set = self._dataset(self.train_data_dir, True, epoch=self.start_epoch)
         test_iter = None
         if self.testing:
             test_set = self._dataset(self.test_data_dir, False)
