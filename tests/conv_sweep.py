@@ -1034,15 +1034,17 @@ def check_e1(d, profile):
 def colsum_roundings(M, C):
     """fp32 roundings on the longest path of one element through the bias gradient ops.conv's backward calls (csrc/elementwise.hip
     vnet_colsum): colsum_vec_kernel -- a thread adds its trips (the first add, to 0, is exact), block_reduce_vec halves 256 threads down
-    to C / 4 -- or, where C / 4 is no power of two, colsum_generic_kernel -- one shared-memory atomicAdd chain per channel and block;
-    then sum_finalize_kernel sums the blocks' rows in float64 and rounds once."""
+    to C / 4 -- or, where C / 4 is no power of two, colsum_generic_kernel -- thread (row group, channel) adds its trips (the first add,
+    to 0, is exact), thread c then adds the G = 256 / C group sums of its channel in group order (the first, to 0, exact; C > 256: one
+    row per block and trip, nothing meets); then sum_finalize_kernel sums the blocks' rows in float64 and rounds once."""
     if C % 4 == 0 and (C // 4) & (C // 4 - 1) == 0 and C // 4 <= 256:
         nq = M * (C // 4)
         nblk = max(1, min(1024, cdiv(nq // 4 + 1, 256)))
         trips = cdiv(nq, nblk * 256)
         return (trips - 1) + (256 // (C // 4)).bit_length() - 1 + 1
     nblk = max(1, min(1024, cdiv(M * C // 4 + 1, 256)))
-    return cdiv(M * C, nblk * 256) * (256 // C + 1) + 1         # (a trip's 256 consecutive elements hold at most 256 // C + 1 of a channel)
+    G = 256 // C if C <= 256 else 1
+    return (cdiv(M, nblk * G) - 1) + (G - 1) + 1
 
 
 def x3_table(rows):

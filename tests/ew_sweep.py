@@ -677,13 +677,17 @@ def _patch_operands(p, lv, rng):
 # ---- the table --------------------------------------------------------------------------------------------------------------------
 class Row(object):
     def __init__(self, name, family, entries, geom, tiers, fixed=None, rot=None, absent=None, clamped=False, nocap=None,
-                 accept=None, kernel="", sizes=None):
+                 accept=None, kernel="", sizes=None, prior=None):
         self.name, self.family, self.entries, self.geom, self.tiers = name, family, tuple(entries), geom, tiers
         self.fixed, self.rot = dict(fixed or {}), collections.OrderedDict(rot or {})
         self.absent = {k: tuple(v[0]) for k, v in (absent or {}).items()}
         self.absent_why = {k: v[1] for k, v in (absent or {}).items()}
         self.clamped, self.nocap, self.accept, self.kernel = clamped, nocap, accept or (lambda p: True), kernel
         self.sizes = sizes                    # a row that is not swept: exactly these extents, one per rotation step
+        # (geometry, absent) the row had when its extents were first chosen, for a kernel whose loop structure changed since: the
+        # cases generated against it stay (an extent is a case whatever it was chosen for), and the generator adds what the
+        # classes of the present geometry still miss
+        self.prior = prior
 
     def needed(self):
         """The (axis, class) pairs the row's cases must realise."""
@@ -741,7 +745,13 @@ def _red_geom(p):
     mode = _red_mode(C)
     if mode == 0:
         return G(M * C // 16 + 1, M * C // 4, U=RED_U)
-    return G(M, M) if mode == 1 else G(M * C // 4 + 1, M * C)
+    return G(M, M) if mode == 1 else _rowgroup_geom(M, C)
+
+
+def _rowgroup_geom(M, C):
+    """The fixed-order generic kernels (bn_act_bwd_reduce_kernel<2>, colsum_generic_kernel, head_bwd_generic_kernel): the grid is
+    sized for a quarter of the elements (+ 1), the loop walks rows, a block takes 256 / C row groups a trip (one row where C > 256)."""
+    return G(M * C // 4 + 1, M, per_block=1 if C > BLOCK else BLOCK // C)
 
 
 def _b16_geom(p):
@@ -795,9 +805,9 @@ def _table():
     add("bn-reduce-m1", "bn", ("vnet_bn_act_bwd_reduce",), _red_geom, E3, red, dict(C=(1, 3, 7), act=acts3, res=(1, 0), bcast=(0, 0, 0, 0, 1)), grid1,
         accept=lambda p: nores(p) and _red_mode(p["C"]) == 1, kernel="bn_act_bwd_reduce_kernel<1>")
     add("bn-reduce-m2", "bn", ("vnet_bn_act_bwd_reduce",), _red_geom, E3, red, dict(C=(12, 37, 255, 300, 13), act=acts3, res=(0, 1), bcast=(0, 0, 0, 0, 1)),
-        {"block": (("eq",), "M * C == 256 only for a power-of-two width, and those are mode 0"), "grid": (("eq", "r1"), "likewise; "
-         "one element past a whole slot needs M * C = 1 modulo 256 * grid with the grid that very extent selects: no width of the row has one")},
-        accept=nores, kernel="bn_act_bwd_reduce_kernel<2>")
+        accept=nores, kernel="bn_act_bwd_reduce_kernel<2>: row groups in a fixed order (C <= 256), a row per block (C = 300)",
+        prior=(lambda p: G(p["M"] * p["C"] // 4 + 1, p["M"] * p["C"]), {"block": (("eq",), "one thread per element: M * C == 256 only for "
+               "a power-of-two width"), "grid": (("eq", "r1"), "likewise")}))
     add("bn-bwd-composite", "bn", ("vnet_bn_act_bwd",), _red_geom, dict(E3, ds="E"), dict(op="bwd"),
         dict(C=(16, 3, 12), act=acts3, res=(0, 1)), sizes=(64, 256, 1024, 256),
         nocap="not a sweep: the composition reduce -> apply (the sums it wrote, M_total = M), exact only where M is a power of two; "
@@ -852,8 +862,8 @@ def _table():
         kernel="head_fwd_kernel<K>, both channel loops")
     add("head-bwd-vec", "head", ("vnet_head_bwd", "vnet_head_ws_bytes"), lambda p: G(p["M"] * (p["C"] // 4) // 4 + 1, p["M"] * (p["C"] // 4)), hb,
         dict(op="bwd"), dict(K=Ks, C=(16, 4, 8)), kernel="head_bwd_kernel<K>")
-    add("head-bwd-generic", "head", ("vnet_head_bwd",), lambda p: G(p["M"] // 4 + 1, p["M"]), hb, dict(op="bwd"), dict(K=Ks, C=(5, 12)),
-        kernel="head_bwd_generic_kernel<K>")
+    add("head-bwd-generic", "head", ("vnet_head_bwd",), lambda p: _rowgroup_geom(p["M"], p["C"]), hb, dict(op="bwd"), dict(K=Ks, C=(5, 12)),
+        kernel="head_bwd_generic_kernel<K>", prior=(lambda p: G(p["M"] // 4 + 1, p["M"]), None))
     add("head16-fwd", "head", ("vnet_head_fwd_b16",), lambda p: G(p["M"] // 2 + 1, p["M"]), {"y": "E"}, dict(op="fwd", b16=1), dict(K=Ks, C=(16, 8, 24)),
         {"grid": (("mult",), "half of the rows + 1, as head-fwd")}, kernel="head_fwd_b16_kernel<K>")
     add("head16-bwd", "head", ("vnet_head_bwd_b16",), _b16_geom, dict(hb, dx="E -> bf16"), dict(op="bwd", b16=1), dict(K=Ks, C=(16, 8, 64, 32)),
@@ -861,8 +871,8 @@ def _table():
     # ---- column sums ----
     add("colsum-vec", "colsum", ("vnet_colsum", "vnet_colsum_ws_bytes"), lambda p: G(p["M"] * (p["C"] // 4) // 4 + 1, p["M"] * (p["C"] // 4)),
         {"out": "E"}, {}, dict(C=(4, 8, 64, 256)), kernel="colsum_vec_kernel")
-    add("colsum-generic", "colsum", ("vnet_colsum",), lambda p: G(p["M"] * p["C"] // 4 + 1, p["M"] * p["C"]), {"out": "E"}, {},
-        dict(C=(1, 3, 12, 37)), kernel="colsum_generic_kernel")
+    add("colsum-generic", "colsum", ("vnet_colsum",), lambda p: _rowgroup_geom(p["M"], p["C"]), {"out": "E"}, {},
+        dict(C=(1, 3, 12, 37)), kernel="colsum_generic_kernel", prior=(lambda p: G(p["M"] * p["C"] // 4 + 1, p["M"] * p["C"]), None))
     add("colsum16", "colsum", ("vnet_colsum_b16", "vnet_colsum_b16_ws_bytes"), _cs16_geom, {"out": "E"}, dict(b16=1), dict(C=(8, 16, 24, 64)),
         {"grid": (("r1", "rm1", "mult"), "one block per 256 / CO rows: every row group has its own block below the cap")},
         kernel="colsum_b16_kernel")
@@ -1001,8 +1011,15 @@ def _extents(row, i, used):
     return out
 
 
-def _gen_row(row):
-    """Phase 1: every rotation step (so every value of every rotated parameter) at a NON-DEGENERATE extent -- the one that realises
+def _prior_row(row):
+    geom, absent = row.prior
+    return Row(row.name, row.family, row.entries, geom, row.tiers, row.fixed, row.rot, absent, row.clamped, row.nocap, row.accept, row.kernel)
+
+
+def _gen_row(row, seed=()):
+    """seed: cases the row keeps from an earlier geometry (Row.prior); they count for what they realise under the present one, phase 1
+    is theirs, and phases 2 and 3 add the rest.
+    Phase 1: every rotation step (so every value of every rotated parameter) at a NON-DEGENERATE extent -- the one that realises
     the most classes still missing; among equals one past the grid's first slot, then one with a ragged block tail, then the
     smallest.  Phase 2: further steps, any extent, until every needed class (lt and eq among them) has occurred.  Phase 3: a rotated
     value that phase 1 never reached at a non-degenerate extent (its step collides with a refused combination) gets the first
@@ -1033,7 +1050,10 @@ def _gen_row(row):
         for i, s in enumerate(row.sizes):
             take(i, s, row.geom(params_of(row, i, s)), set())
         return cases
-    for i in range(nrot):
+    for c in seed:
+        g = row.geom(params_of(row, c.i, c.size))
+        take(c.i, c.size, g, set(classes(g).items()) & need)
+    for i in range(0 if seed else nrot):
         cands = [(s, g) for s, g in _extents(row, i, used) if nondegenerate(g, s)]
         if cands:
             take(i, *best_of(cands, i))
@@ -1084,11 +1104,15 @@ _CASES = []
 def generate():
     if not _CASES:
         for row in ROWS.values():
-            cs = _gen_row(row)
+            first = _prior_row(row) if row.prior else row
+            cs = _gen_row(first)
+            if row.prior:
+                cs = _gen_row(row, seed=cs)
             _CASES.extend(cs)
             if row.nocap is None:
                 # the cheapest parameters for the big case: the rotation step whose capped extent holds the fewest elements
-                cands = [_capped_case(row, c.i) for c in cs]
+                # (a row with a prior geometry keeps that geometry's big case: wraps() holds it to the present launch all the same)
+                cands = [_capped_case(first, c.i) for c in cs]
                 _CASES.append(min(cands, key=lambda c: (case_params(c).get("K", 2) < 2, _elements(c))))     # (not the one-class softmax)
     return list(_CASES)
 

@@ -54,7 +54,6 @@ class Arena(object):
         self.entries = []
         self.cursor = 0
         self.demoted = []             # (entry point, parameter, tensor) of `in` tensors a call took as a destination
-        self.atomic_outputs = set()   # names of tensors vnet_colsum wrote
 
     # ---- carving -------------------------------------------------------------------------------------------------------
     def guard_bytes(self, shape, dtype):
@@ -248,8 +247,6 @@ class RecordingLib(object):
                 if not _const and e.role == "in":          # the caller handed one of its tensors over as a destination (y +=, p -=)
                     e.role, e.host = "inout", None
                     self._arena.demoted.append((name, pname, e.name))
-                if not _const and name == "vnet_colsum" and pname == "out":
-                    self._arena.atomic_outputs.add(e.name)          # colsum_generic_kernel may have produced it (LDS float atomics)
             return fn(*args)
         return call
 

@@ -339,10 +339,12 @@ def test_x3_six_stream_emulation_equals_the_oracle(case, profile):
 
 
 def test_colsum_roundings_counts_the_vector_and_the_generic_kernel():
-    """The counted bound of the dy-deep bias gradient: trips - 1 + log2(256 / (C / 4)) + 1 roundings in the vector kernel, the atomic
-    chain of a block + 1 in the generic one (C / 4 no power of two: the 48-channel cases)."""
+    """The counted bound of the dy-deep bias gradient: trips - 1 + log2(256 / (C / 4)) + 1 roundings in the vector kernel; a thread's
+    trips - 1, the 256 / C - 1 additions of the group sums in their fixed order and + 1 in the generic one (C / 4 no power of two: the
+    48-channel cases)."""
     assert S.colsum_roundings(1024, 16) == 3 + 6 + 1                      # 4096 float4 on 5 blocks (a block per 1024): 4 trips
     assert S.colsum_roundings(1024 * 256 * 3, 16) == 11 + 6 + 1           # the grid cap, 1024 blocks: 12 trips
     assert S.colsum_roundings(1024, 32) == 3 + 5 + 1
-    assert S.colsum_roundings(64, 48) == 3 * (256 // 48 + 1) + 1          # 3072 elements on 4 blocks: 3 trips of <= 6 of a channel
+    assert S.colsum_roundings(64, 48) == 3 + 4 + 1                        # 64 rows on 4 blocks of 5 row groups: 4 trips, 5 groups meet
+    assert S.colsum_roundings(7, 300) == 2 + 0 + 1                        # 7 rows on 3 blocks, a row per block and trip: 3 trips, nothing meets
     assert any(c.O == 48 for c in X3_CASES) and any(c.O in (16, 32) for c in X3_CASES)

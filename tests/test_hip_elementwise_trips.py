@@ -91,7 +91,7 @@ def _bn_wraps(tag, M, C, tile=False, stats=True, reduce=True, apply=True):
         elif mode == 1:
             _wraps(tag + " reduce row", M)
         else:
-            _wraps(tag + " reduce generic", M * C // 4 + 1, items=M * C)
+            _wraps(tag + " reduce generic", M * C // 4 + 1, items=M, per_block=1 if C > BLOCK else BLOCK // C)     # (row groups)
 
 
 # ---- batch-norm, float32 -----------------------------------------------------------------------------------------------------------
@@ -189,7 +189,7 @@ def test_colsum(dev, C):
     if _red_mode(C) == 0:
         _wraps("colsum vec", M * (C // 4) // 4 + 1, items=M * (C // 4))
     else:
-        _wraps("colsum generic", M * C // 4 + 1, items=M * C)
+        _wraps("colsum generic", M * C // 4 + 1, items=M, per_block=BLOCK // C)              # (256 / C row groups per block)
     x = np.random.default_rng(C).standard_normal((M, C)).astype(np.float32)
     got = ops.colsum(torch.from_numpy(x).to(dev), C)
     x64 = x.astype(np.float64)
@@ -223,7 +223,7 @@ def test_activation(dev, act, C):
 
 @pytest.mark.parametrize("C,K", [(16, 2), (16, 5), (8, 8), (5, 3), (6, 2)])
 def test_head(dev, C, K):
-    """ops.head_conv: head_fwd_kernel (M / 2), head_bwd_kernel (M C / 16) or head_bwd_generic_kernel (M / 4), each past its own trip.
+    """ops.head_conv: head_fwd_kernel (M / 2), head_bwd_kernel (M C / 16) or head_bwd_generic_kernel (M C / 4), each past its own trip.
     The bars of test_head."""
     from vnet_tensorflow_amd import ops
     vec = _red_mode(C) == 0
@@ -232,7 +232,7 @@ def test_head(dev, C, K):
     if vec:
         _wraps("head bwd vec", M * (C // 4) // 4 + 1, items=M * (C // 4))
     else:
-        _wraps("head bwd generic", M // 4 + 1, items=M)
+        _wraps("head bwd generic", M * C // 4 + 1, items=M, per_block=BLOCK // C)            # (256 / C row groups per block)
     rng = np.random.default_rng(C * K)
     x = rng.standard_normal((M, C)).astype(np.float32).astype(np.float64)
     w = rng.standard_normal((1, 1, 1, C, K)).astype(np.float32).astype(np.float64)

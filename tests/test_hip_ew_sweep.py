@@ -430,3 +430,24 @@ def test_ew_sweep(dev, case):
         _check(case, name, tier, got[name], exp[name], exp.get(name + "~"))
         checked += 1
     assert checked == len(got) and checked > 0, (S.cid(case), sorted(got), sorted(row.tiers))
+
+
+# ---- the wide-row branch (C > 256) of colsum_generic_kernel and head_bwd_generic_kernel ----------------------------------------------
+# The table's rows rotate C = 1 .. 37 for these two kernels (bn-reduce-m2 has C = 300); their branch for rows wider than a block --
+# a row per block and trip, a thread owns the columns tid + j * 256 -- runs here, on integer operands whose sums are exact: `==`.
+@pytest.mark.parametrize("C,K,M", [(300, 3, 1531), (257, 2, 5), (1021, 1, 1100)])
+def test_generic_kernels_wide_rows(dev, C, K, M):
+    rng = np.random.default_rng(C * K + M)
+    d = {"x": S._ints(rng, 3, (M, C)), "w": S._ints(rng, 3, (C, K)), "bias": S._ints(rng, 3, K), "dy": S._ints(rng, 3, (M, K))}
+    assert np.abs(d["x"]).sum(0).max() * 9 < S.LIMIT                            # (every partial sum exact in float32)
+    with _guarded(dev) as h:
+        env = Env(dev, h)
+        got = run_colsum(env, dict(M=M, C=C), d)
+        got.update(run_head(env, dict(M=M, C=C, K=K, op="bwd"), d))
+        torch.cuda.synchronize()
+        got = {k: _np(v) for k, v in got.items()}
+    want = {"out": d["x"].sum(0), "dx": d["dy"] @ d["w"].T, "dw": d["x"].T @ d["dy"], "db": d["dy"].sum(0)}
+    for name in sorted(want):
+        bad = np.nonzero(~(got[name].reshape(-1) == want[name].reshape(-1)))[0]
+        assert bad.size == 0, "C = %d, K = %d, M = %d: output `%s`: %d of %d elements wrong, first at %d" % (
+            C, K, M, name, bad.size, want[name].size, int(bad[0]))

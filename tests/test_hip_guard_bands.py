@@ -5,8 +5,8 @@ with all its device buffers carved from one arena: inputs, every tensor ops allo
 vnet_packed_weight_floats floats, and ops.workspace() replaced by arena scratch of EXACTLY the bytes route() reported.  A device
 pointer outside the arena fails the case.  Checked: (a) no guard byte touched, no input changed; (b) no `out` element left
 unwritten; (c) the result against the fp64 oracle -- the case functions and tolerances ARE the existing tests' (imported, not
-restated); (d) the run on 0xFF-filled and the run on 0x00-filled outputs and scratch agree bit for bit, except for the kernels of
-ATOMIC_KERNELS, which add through LDS float atomics in an order the hardware picks.
+restated); (d) the run on 0xFF-filled and the run on 0x00-filled outputs and scratch agree bit for bit -- for every case: ATOMIC_KERNELS,
+the kernels that once added through LDS float atomics in an order the hardware picks, is empty (tests/test_hip_determinism.py).
 
 COVERED, EXEMPT, FAMILIES and the case table are what tests/test_host.py's ledger reads.  The 5x5x1 convolution (kx = 1) runs in the
 input-im2col cases, the bf16 conv2-direct `up` launch in b16-conv2-direct-odd-b2 (forward of the transposed layer and backward-data
@@ -25,8 +25,9 @@ from tests.util import check_close
 
 pytestmark = pytest.mark.gpu
 
-# elementwise.hip kernels that add floats with atomicAdd (LDS): held to (a)-(c) only -- the order of the adds is the hardware's
-ATOMIC_KERNELS = ("bn_act_bwd_reduce_kernel", "colsum_generic_kernel", "head_bwd_generic_kernel")
+# elementwise.hip kernels that add floats with atomicAdd (LDS) would be held to (a)-(c) only: there are none (tests/test_host.py holds
+# this tuple against the source; the generic batch-norm reduce, column sum and head backward had such adds and keep their case ids)
+ATOMIC_KERNELS = ()
 
 
 def _split3(fn):
@@ -433,10 +434,6 @@ IN_DIRECT = ("vnet_input_conv_fold", "vnet_input_conv_fold_border", "vnet_input_
 IN_IM2COL = ("vnet_input_conv_fold", "vnet_tile_im2col_x", "vnet_conv_fwd", "vnet_conv_wgrad", "vnet_input_conv_grads", PACK,
              "vnet_bn_stats", "vnet_bn_act_fwd", "vnet_bn_act_bwd_reduce", COLSUM)
 
-# (d) for a convolution whose channel count is off the column sum's vector path (5, 48): everything but the bias gradient, which
-# colsum_generic_kernel adds through LDS float atomics -- identified as the tensor vnet_colsum was handed as `out`
-DB_ATOMIC = "colsum-out"
-
 # id -> (entry points the case must reach, families / batch-norm routes it must take, deterministic (d), the case)
 CASES = {
     # ---- fp32 MFMA convolutions: forward, backward-data (two destinations with a second source), filter gradient, bias gradient
@@ -448,7 +445,7 @@ CASES = {
     "conv5-1x1x1-b3": (CONV5, ("conv", "wgrad"), True, _conv(5, 1, 3, 1, 1, 1, 16, 0, 16)),
     "conv5-narrow-channels": (CONV5, ("conv", "wgrad"), True, _conv(5, 1, 1, 6, 7, 9, 4, 4, 8)),
     "conv5-cin3-gather": (CONV5, ("conv", "wgrad"), True, _conv(5, 1, 1, 6, 6, 18, 3, 0, 16)),
-    "conv5-cout5-scatter": (CONV5, ("conv", "wgrad"), DB_ATOMIC, _conv(5, 1, 1, 4, 6, 16, 16, 0, 5)),
+    "conv5-cout5-scatter": (CONV5, ("conv", "wgrad"), True, _conv(5, 1, 1, 4, 6, 16, 16, 0, 5)),
     "down-direct-f32": (("vnet_conv2_direct_f32", "vnet_conv_wgrad", COLSUM), ("conv2-direct", "wgrad"), True,
                         _conv(2, 2, 1, 8, 16, 32, 16, 0, 32)),
     "down-direct-f32-odd-b2": (("vnet_conv2_direct_f32", "vnet_conv_wgrad", COLSUM), ("conv2-direct", "wgrad"), True,
@@ -466,9 +463,9 @@ CASES = {
     "x3-wide-ragged-two-source-b2": (X3, ("conv-x3", "wgrad-x3"), True, _split3(_conv(5, 1, 2, 5, 9, 17, 16, 16, 16))),
     "x3-two-cout-blocks": (X3, ("conv-x3", "wgrad-x3"), True, _split3(_conv(5, 1, 1, 8, 8, 16, 32, 0, 32))),
     "x3-k-split": (X3, ("conv-x3", "wgrad-x3"), True, _split3(_conv(5, 1, 1, 8, 8, 16, 128, 0, 32))),
-    "x3-8-wide-ragged-b2": (X3, ("conv-x3", "wgrad-x3"), DB_ATOMIC, _split3(_conv(5, 1, 2, 6, 10, 8, 16, 16, 48))),
+    "x3-8-wide-ragged-b2": (X3, ("conv-x3", "wgrad-x3"), True, _split3(_conv(5, 1, 2, 6, 10, 8, 16, 16, 48))),
     "x3-8-wide-k-split": (X3, ("conv-x3", "wgrad-x3"), True, _split3(_conv(5, 1, 1, 8, 8, 8, 128, 0, 64))),
-    "x3-smaller-than-a-brick": (X3, ("conv-x3", "wgrad-x3"), DB_ATOMIC, _split3(_conv(5, 1, 1, 3, 5, 7, 16, 0, 48))),
+    "x3-smaller-than-a-brick": (X3, ("conv-x3", "wgrad-x3"), True, _split3(_conv(5, 1, 1, 3, 5, 7, 16, 0, 48))),
     # ---- bf16 storage
     "b16-conv5-ragged-two-source-b2": (("vnet_conv_fwd_b16", "vnet_conv_wgrad_b16", "vnet_colsum_b16", PACK), ("conv-bf16", "wgrad-bf16"),
                                        True, lambda fx: T16.test_conv5_b16_against_oracle_and_fp32_output_kernels(
@@ -492,17 +489,17 @@ CASES = {
                             _direct(True, lambda fx: TO._input_block_case(fx.dev, (1, 8, 8, 8, 8), True))),
     "input-im2col-ragged": (IN_IM2COL, ("conv", "wgrad"), True, _direct(False, lambda fx: TO._input_block_case(fx.dev, (2, 5, 9, 17, 16), False))),
     "input-im2col-4ch": (IN_IM2COL, ("conv", "wgrad"), True, _direct(True, lambda fx: TO._input_block_case(fx.dev, (1, 6, 7, 9, 4), True))),
-    # ---- batch-norm (fp32): vector path, row path (C <= 8), generic path (LDS float atomics in the backward reduce), tile
+    # ---- batch-norm (fp32): vector path, row path (C <= 8), generic path (fixed-order LDS meeting in both passes), tile
     "bn-vec-res": (BN, ("stream",), True, lambda fx: TO._bn_act_case(fx.dev, 16, "prelu", True, False, (2, 5, 6, 7), 23)),
     "bn-vec-256": (BN, ("stream",), True, lambda fx: TO._bn_act_case(fx.dev, 256, "prelu", True, False, (1, 3, 3, 7), 24)),
     "bn-row-c5": (BN, ("stream",), True, lambda fx: TO._bn_act_case(fx.dev, 5, "lrelu", True, False, (2, 5, 6, 7), 12)),
-    "bn-generic-c12-atomic": (BN, ("stream",), False, lambda fx: TO._bn_act_case(fx.dev, 12, "prelu", False, False, (3, 5, 6, 7), 12)),
+    "bn-generic-c12-atomic": (BN, ("stream",), True, lambda fx: TO._bn_act_case(fx.dev, 12, "prelu", False, False, (3, 5, 6, 7), 12)),
     "bn-tile": (BN, ("stream",), True, lambda fx: TO._bn_act_case(fx.dev, 16, None, False, True, (2, 5, 6, 7), 16)),
     "bn-chain-kind0": (CHAIN, ("stream",), True, lambda fx: TO.test_bn_chain(fx.dev, 0, 16, "prelu")),
     "bn-chain-kind1": (CHAIN, ("stream",), True, lambda fx: TO.test_bn_chain(fx.dev, 1, 64, "lrelu")),
     # ---- head, loss, activation, metrics, dropout
     "head-vec": (("vnet_head_fwd", "vnet_head_bwd"), (), True, lambda fx: TO.test_head(fx.dev, 16, 5)),
-    "head-generic-atomic": (("vnet_head_fwd", "vnet_head_bwd"), (), False, lambda fx: TO.test_head(fx.dev, 6, 2)),
+    "head-generic-atomic": (("vnet_head_fwd", "vnet_head_bwd"), (), True, lambda fx: TO.test_head(fx.dev, 6, 2)),
     "act-prelu": (("vnet_act_fwd", "vnet_act_bwd"), (), True, lambda fx: TO.test_activation_standalone(fx.dev)),
     "confusion-matrix": (("vnet_confusion_matrix",), (), True, lambda fx: TO.test_hard_metrics(fx.dev)),
     # ---- epilogue statistics into exactly Route.stats_rows rows, the finalize from them, y += conv (in and out of place)
@@ -601,14 +598,14 @@ def _run(cid, fx, poison):
     finally:
         for n, f in real.items():
             fx.monkeypatch.setattr(ops, n, f)
-    return arena.snapshot(), h.calls, seen, set(arena.atomic_outputs)
+    return arena.snapshot(), h.calls, seen
 
 
 @pytest.mark.parametrize("cid", sorted(CASES))
 def test_guard_bands(dev, cid, monkeypatch, lib_option):
     entries, fams, det, fn = CASES[cid]
     fx = _Fx(dev, monkeypatch, lib_option)
-    snap_ff, calls, seen, colsum_out = _run(cid, fx, guard.GUARD)
+    snap_ff, calls, seen = _run(cid, fx, guard.GUARD)
     missing = set(entries) - set(calls)
     assert not missing, "%s never reached %s (called: %s)" % (cid, sorted(missing), sorted(set(calls)))
     table = guard.pointer_entry_points()
@@ -616,7 +613,5 @@ def test_guard_bands(dev, cid, monkeypatch, lib_option):
     assert not undeclared, "%s also runs %s: name them in its row" % (cid, sorted(undeclared))
     assert set(fams) <= seen, "%s: expected the routes %s, took %s" % (cid, fams, sorted(seen))
     if det:
-        snap_00, _, _, _ = _run(cid, fx, 0x00)
-        skip = colsum_out if det == DB_ATOMIC else ()
-        assert det != DB_ATOMIC or len(skip) == 1, skip
-        guard.assert_same_bits([t for t in snap_ff if t[0] not in skip], [t for t in snap_00 if t[0] not in skip])          # (d)
+        snap_00, _, _ = _run(cid, fx, 0x00)
+        guard.assert_same_bits(snap_ff, snap_00)          # (d)

@@ -467,22 +467,59 @@ __global__ void __launch_bounds__(EW_BLOCK) bn_act_bwd_reduce_kernel(BnP p) {
         }
         block_reduce_row<3, 8>(acc, C, p.partial + (size_t)blockIdx.x * 3 * C);
     } else {
-        __shared__ float sh[3 * MAXC];
-        for (int c = threadIdx.x; c < 3 * C; c += EW_BLOCK) sh[c] = 0.f;
-        __syncthreads();
-        const size_t n = p.M * C;
-        for (size_t idx = start; idx < n; idx += stride) {
-            const int c = (int)(idx % C);
-            float v = p.bcast ? p.x[idx / C] : p.x[idx];
+        // any other channel count, in a fixed order like bn_stats_generic_kernel (this mode used LDS float atomics before, whose
+        // sums depended on the order in which the waves arrived).  C <= 256: thread = (row group rg, channel c), G = 256 / C row
+        // groups per block; a thread adds its own rows blockIdx * G + rg + t * gridDim * G in trip order t = 0, 1, ...; thread c then
+        // adds the G group sums from LDS in the order rg = 0 .. G - 1.  C > 256: a block takes the rows blockIdx + t * gridDim in
+        // trip order, a thread owns the columns tid + j * 256 and no sums meet.  One partial row [3][C] per block either way.
+        float* prow = p.partial + (size_t)blockIdx.x * 3 * C;
+        auto terms = [&](size_t row, int c, float mu, float is, float& a0, float& a1, float& a2) {
+            const size_t idx = row * C + c;
+            float v = p.bcast ? p.x[row] : p.x[idx];
             if (p.r) v += p.r[idx];
             const float g = p.dy[idx];
             const float z = v * sc[c] + sf[c];
             const float dz = g * act_grad(z, p.act, al[c]);
-            atomicAdd(&sh[c], dz); atomicAdd(&sh[C + c], p.identity ? 0.f : dz * (v - p.mean[c]) * p.invstd[c]);
-            atomicAdd(&sh[2 * C + c], g * fminf(z, 0.f));
+            a0 += dz; a1 += p.identity ? 0.f : dz * (v - mu) * is; a2 += g * fminf(z, 0.f);
+        };
+        if (C > EW_BLOCK) {
+            constexpr int NCOL = MAXC / EW_BLOCK;
+            float a0[NCOL], a1[NCOL], a2[NCOL], mu[NCOL], is[NCOL];
+#pragma unroll
+            for (int j = 0; j < NCOL; ++j) {
+                const int c = threadIdx.x + j * EW_BLOCK;
+                a0[j] = a1[j] = a2[j] = 0.f;
+                mu[j] = (p.identity || c >= C) ? 0.f : p.mean[c]; is[j] = (p.identity || c >= C) ? 0.f : p.invstd[c];
+            }
+            for (size_t row = blockIdx.x; row < p.M; row += gridDim.x) {
+#pragma unroll
+                for (int j = 0; j < NCOL; ++j) {
+                    const int c = threadIdx.x + j * EW_BLOCK;
+                    if (c < C) terms(row, c, mu[j], is[j], a0[j], a1[j], a2[j]);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NCOL; ++j) {
+                const int c = threadIdx.x + j * EW_BLOCK;
+                if (c < C) { prow[c] = a0[j]; prow[C + c] = a1[j]; prow[2 * C + c] = a2[j]; }
+            }
+        } else {
+            __shared__ float sh[3][EW_BLOCK];
+            const int G = EW_BLOCK / C;
+            const int rg = threadIdx.x / C, c = threadIdx.x - rg * C;
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+            if (rg < G) {
+                const float mu = p.identity ? 0.f : p.mean[c], is = p.identity ? 0.f : p.invstd[c];
+                for (size_t row = (size_t)blockIdx.x * G + rg; row < p.M; row += (size_t)gridDim.x * G) terms(row, c, mu, is, a0, a1, a2);
+            }
+            sh[0][threadIdx.x] = a0; sh[1][threadIdx.x] = a1; sh[2][threadIdx.x] = a2;
+            __syncthreads();
+            if (threadIdx.x < C) {
+                float t0 = 0.f, t1 = 0.f, t2 = 0.f;
+                for (int g = 0; g < G; ++g) { t0 += sh[0][g * C + threadIdx.x]; t1 += sh[1][g * C + threadIdx.x]; t2 += sh[2][g * C + threadIdx.x]; }
+                prow[threadIdx.x] = t0; prow[C + threadIdx.x] = t1; prow[2 * C + threadIdx.x] = t2;
+            }
         }
-        __syncthreads();
-        for (int c = threadIdx.x; c < 3 * C; c += EW_BLOCK) p.partial[(size_t)blockIdx.x * 3 * C + c] = sh[c];
     }
 }
 
@@ -552,14 +589,45 @@ __global__ void __launch_bounds__(EW_BLOCK) colsum_vec_kernel(const float4* __re
     }
     block_reduce_vec<1>(acc, CQ, CQ * 4, partial + (size_t)blockIdx.x * CQ * 4);
 }
+// any other channel count, in the fixed order of bn_stats_generic_kernel (LDS float atomics before: the sums followed the arrival
+// of the waves).  C <= 256: thread = (row group rg, channel c), G = 256 / C groups per block; a thread adds its rows
+// blockIdx * G + rg + t * gridDim * G in trip order, thread c then adds the G group sums from LDS in the order rg = 0 .. G - 1.
+// C > 256: a block takes the rows blockIdx + t * gridDim in trip order, a thread owns the columns tid + j * 256, no sums meet.
 __global__ void __launch_bounds__(EW_BLOCK) colsum_generic_kernel(const float* __restrict__ x, size_t n, int C, float* __restrict__ partial) {
-    __shared__ float sh[MAXC];
-    for (int c = threadIdx.x; c < C; c += EW_BLOCK) sh[c] = 0.f;
+    __shared__ float sh[EW_BLOCK];
+    const size_t M = n / C;
+    float* prow = partial + (size_t)blockIdx.x * C;
+    if (C > EW_BLOCK) {
+        constexpr int NCOL = MAXC / EW_BLOCK;
+        float s[NCOL];
+#pragma unroll
+        for (int j = 0; j < NCOL; ++j) s[j] = 0.f;
+        for (size_t row = blockIdx.x; row < M; row += gridDim.x) {
+#pragma unroll
+            for (int j = 0; j < NCOL; ++j) {
+                const int c = threadIdx.x + j * EW_BLOCK;
+                if (c < C) s[j] += x[row * C + c];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NCOL; ++j) {
+            const int c = threadIdx.x + j * EW_BLOCK;
+            if (c < C) prow[c] = s[j];
+        }
+        return;
+    }
+    const int G = EW_BLOCK / C;
+    const int rg = threadIdx.x / C, c = threadIdx.x - rg * C;
+    float s = 0.f;
+    if (rg < G)
+        for (size_t row = (size_t)blockIdx.x * G + rg; row < M; row += (size_t)gridDim.x * G) s += x[row * C + c];
+    sh[threadIdx.x] = s;
     __syncthreads();
-    const size_t stride = (size_t)gridDim.x * EW_BLOCK;
-    for (size_t idx = (size_t)blockIdx.x * EW_BLOCK + threadIdx.x; idx < n; idx += stride) atomicAdd(&sh[idx % C], x[idx]);
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += EW_BLOCK) partial[(size_t)blockIdx.x * C + c] = sh[c];
+    if (threadIdx.x < C) {
+        float t = 0.f;
+        for (int g = 0; g < G; ++g) t += sh[g * C + threadIdx.x];
+        prow[threadIdx.x] = t;
+    }
 }
 
 // ---- 1x1x1 output head (C -> K<=8) ----------------------------------------------------------
@@ -651,32 +719,97 @@ __global__ void __launch_bounds__(EW_BLOCK) head_bwd_kernel(const float* __restr
     }
 }
 
-// any C (not a multiple of 4 / no power-of-two quad count): one thread per row, LDS accumulation of dw / db
+// any C (not a multiple of 4 / no power-of-two quad count), in the fixed order of bn_stats_generic_kernel (one thread per row and
+// LDS float atomics on dw / db before: the sums followed the arrival of the waves).  C <= 256: thread = (row group rg, channel c),
+// G = 256 / C groups per block; a thread adds x * dy of its rows blockIdx * G + rg + t * gridDim * G in trip order (the thread of
+// channel 0 also dy itself, for db); thread c then adds the G group sums from LDS in the order rg = 0 .. G - 1, class by class.
+// C > 256: a block takes the rows blockIdx + t * gridDim in trip order, a thread owns the columns tid + j * 256, no sums meet.
 template <int K>
 __global__ void __launch_bounds__(EW_BLOCK) head_bwd_generic_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                     const float* __restrict__ dy, float* __restrict__ dx,
                                                                     size_t M, int C, float* __restrict__ partial) {
     __shared__ float ws[1024];
-    __shared__ float acc[1024 + 8];
+    __shared__ float red[K][EW_BLOCK];
     for (int t = threadIdx.x; t < C * K; t += EW_BLOCK) ws[t] = w[t];
-    for (int t = threadIdx.x; t < C * K + K; t += EW_BLOCK) acc[t] = 0.f;
     __syncthreads();
-    const size_t stride = (size_t)gridDim.x * EW_BLOCK;
-    for (size_t row = (size_t)blockIdx.x * EW_BLOCK + threadIdx.x; row < M; row += stride) {
-        float g[K];
+    float* prow = partial + (size_t)blockIdx.x * (C * K + K);
+    if (C > EW_BLOCK) {
+        constexpr int NCOL = 1024 / EW_BLOCK;
+        float aw[NCOL][K], ab[K];
 #pragma unroll
-        for (int k = 0; k < K; ++k) { g[k] = dy[row * K + k]; atomicAdd(&acc[C * K + k], g[k]); }
-        for (int c = 0; c < C; ++c) {
+        for (int k = 0; k < K; ++k) {
+            ab[k] = 0.f;
+#pragma unroll
+            for (int j = 0; j < NCOL; ++j) aw[j][k] = 0.f;
+        }
+        for (size_t row = blockIdx.x; row < M; row += gridDim.x) {
+            float g[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) { g[k] = dy[row * K + k]; ab[k] += g[k]; }
+#pragma unroll
+            for (int j = 0; j < NCOL; ++j) {
+                const int c = threadIdx.x + j * EW_BLOCK;
+                if (c < C) {
+                    const float v = x[row * C + c];
+                    float o = 0.f;
+#pragma unroll
+                    for (int k = 0; k < K; ++k) { o += g[k] * ws[c * K + k]; aw[j][k] += v * g[k]; }
+                    if (dx) dx[row * C + c] = o;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NCOL; ++j) {
+            const int c = threadIdx.x + j * EW_BLOCK;
+            if (c < C) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) prow[c * K + k] = aw[j][k];
+            }
+        }
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) prow[C * K + k] = ab[k];
+        }
+        return;
+    }
+    const int G = EW_BLOCK / C;
+    const int rg = threadIdx.x / C, c = threadIdx.x - rg * C;
+    float aw[K], ab[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) aw[k] = ab[k] = 0.f;
+    if (rg < G) {
+        for (size_t row = (size_t)blockIdx.x * G + rg; row < M; row += (size_t)gridDim.x * G) {
             const float v = x[row * C + c];
-            float o = 0.f;
+            float g[K], o = 0.f;
 #pragma unroll
-            for (int k = 0; k < K; ++k) { o += g[k] * ws[c * K + k]; atomicAdd(&acc[c * K + k], v * g[k]); }
+            for (int k = 0; k < K; ++k) { g[k] = dy[row * K + k]; o += g[k] * ws[c * K + k]; aw[k] += v * g[k]; ab[k] += g[k]; }
             if (dx) dx[row * C + c] = o;
         }
     }
+    // dw: the group sums of channel c, groups in increasing order
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[k][threadIdx.x] = aw[k];
     __syncthreads();
-    float* prow = partial + (size_t)blockIdx.x * (C * K + K);
-    for (int t = threadIdx.x; t < C * K + K; t += EW_BLOCK) prow[t] = acc[t];
+    if (threadIdx.x < C) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            float t = 0.f;
+            for (int g = 0; g < G; ++g) t += red[k][g * C + threadIdx.x];
+            prow[threadIdx.x * K + k] = t;
+        }
+    }
+    __syncthreads();
+    // db: what the threads of channel 0 summed, groups in increasing order
+    if (rg < G && c == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) red[k][rg] = ab[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        float t = 0.f;
+        for (int g = 0; g < G; ++g) t += red[threadIdx.x][g];
+        prow[C * K + threadIdx.x] = t;
+    }
 }
 
 // ---- the decoder's last batch-norm fused with the 1x1x1 head behind it (include/vnet_hip_head.h) --------------------------------
@@ -2134,7 +2267,7 @@ int vnet_head_bwd(const float* x, const float* w, const float* dy, float* dx, fl
             return launch<head_bwd_kernel<KK>>(dim3(nblk), dim3(EW_BLOCK), 0, st, x, w, dy, dx, (size_t)M, C, partial);
         });
     } else {
-        nblk = ew_blocks((size_t)M / 4 + 1);
+        nblk = ew_blocks((size_t)M * C / 4 + 1);     // (a thread per element and about four trips, as vnet_colsum)
         e = with_k(K, [&](auto KK) {
             return launch<head_bwd_generic_kernel<KK>>(dim3(nblk), dim3(EW_BLOCK), 0, st, x, w, dy, dx, (size_t)M, C, partial);
         });
