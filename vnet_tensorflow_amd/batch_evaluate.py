@@ -16,7 +16,10 @@ What differs from the reference, on purpose:
   * patch_size / patch_layer reach the model: they replace TrainingSetting.PatchShape by [patch_size, patch_size, patch_layer]; None
     keeps the config's value (the reference's constructor drops both arguments).
   * The flags are parsed from the real command line, not from the string main.py hard-codes; --mode, --tolerance and --gpu are
-    added."""
+    added.
+  * --mode SURFACE (not in the reference) adds HD, HD95 and ASSD of the foreground surface in physical units, by the rules of score.py;
+    on a device model an exact Euclidean distance transform runs there (vnet_tensorflow_amd/surface.py).  A case in which exactly one
+    of the two maps has no foreground scores inf, and so does the `average` row."""
 import argparse
 import copy
 import csv
@@ -30,6 +33,7 @@ from . import data as vdata
 from . import score
 
 ITEM_COLUMNS = ["TP", "FP", "FN", "Item Sensitivity", "Item IoU"]
+SURFACE_COLUMNS = ["HD", "HD95", "ASSD"]
 _CKPT = re.compile(r"^checkpoint-(\d+)(\.index)?$")
 
 
@@ -50,6 +54,8 @@ def columns(mode):
         cols += ["DICE", "Jaccard"]
     if "ITEM" in mode:
         cols += ITEM_COLUMNS
+    if "SURFACE" in mode:
+        cols += SURFACE_COLUMNS
     return cols
 
 
@@ -93,7 +99,8 @@ class Batch_Evaluate:
                  tolerance=3,
                  device=None,
                  write_labels=False,
-                 verbose=False):
+                 verbose=False,
+                 cache_fields=True):
         self.config_json = config_json               # a path, or the parsed dict
         self.model_folder = model_folder
         self.output_folder = output_folder
@@ -115,12 +122,14 @@ class Batch_Evaluate:
         assert patch_layer is None or (isinstance(patch_layer, int) and patch_layer > 0)
         self.patch_size, self.patch_layer = patch_size, patch_layer
         self.batch_size = batch_size
-        self.mode = list(mode)                       # DICE, ITEM
-        assert self.mode and all(m in ("DICE", "ITEM") for m in self.mode), mode
+        self.mode = list(mode)                       # DICE, ITEM, SURFACE
+        assert self.mode and all(m in ("DICE", "ITEM", "SURFACE") for m in self.mode), mode
         self.tolerance = tolerance
         self.device = device
         self.write_labels = bool(write_labels)
         self.verbose = bool(verbose)
+        # SURFACE: keep every case's ground-truth surface and its squared distance field (8 bytes per voxel) over the sweep
+        self.cache_fields = bool(cache_fields)
 
     @property
     def model_folder(self):
@@ -190,7 +199,8 @@ class Batch_Evaluate:
 
     def _case(self, model, name, cache):
         """What a case keeps over the whole sweep: the input image (host), its spacing, the remapped ground truth where the model's
-        labels live (uploaded once) and, for ITEM, the ground truth's component shapes (computed once)."""
+        labels live (uploaded once), for ITEM the ground truth's component shapes (computed once) and, for SURFACE with cache_fields,
+        the ground truth's surface and squared distance field (computed once; on the device for a device model)."""
         entry = cache.get(name)
         if entry is None:
             cdir = os.path.join(self._data_folder, name)
@@ -207,6 +217,7 @@ class Batch_Evaluate:
                      # (the reference sets the ground truth's spacing on the output before it measures)
                      "gt_spacing": vdata.volume_spacing(gt_path),
                      "gt_shapes": score.shapes_of(gt) if "ITEM" in self.mode else None}
+            entry["gt_field"] = score.surface_field(gt, entry["gt_spacing"]) if "SURFACE" in self.mode and self.cache_fields else None
             cache[name] = entry
         return entry
 
@@ -221,7 +232,8 @@ class Batch_Evaluate:
         if hasattr(label, "contiguous"):
             label = label.contiguous()
         return score.Accuracy(gt, label, spacing=entry["gt_spacing"], tolerence=self.tolerance, mode=self.mode,
-                              L=max(2, min(len(model.label_classes), score.MAX_LABELS)), gt_shapes=entry["gt_shapes"])
+                              L=max(2, min(len(model.label_classes), score.MAX_LABELS)), gt_shapes=entry["gt_shapes"],
+                              gt_field=entry["gt_field"])
 
     def Execute(self):
         model = self.build_model(self.config())
@@ -306,7 +318,8 @@ def get_args(argv=None):
                         default="./config.json")
     parser.add_argument('-o', '--output', dest='output', help='Output directory', type=readable_dir, metavar='DIR', default="./tmp")
     # additions
-    parser.add_argument('--mode', dest='mode', help='Scores to compute', nargs='+', choices=["DICE", "ITEM"], default=["DICE"])
+    parser.add_argument('--mode', dest='mode', help='Scores to compute', nargs='+', choices=["DICE", "ITEM", "SURFACE"],
+                        default=["DICE"])
     parser.add_argument('--tolerance', dest='tolerance', help='Centroid distance below which an item is found (ITEM)', type=float,
                         metavar='FLOAT', default=3)
     parser.add_argument('--gpu', dest='gpu', help='Index of the HIP device', type=int, metavar='INT', default=0)
