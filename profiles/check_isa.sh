@@ -13,6 +13,8 @@ for f in deform_sample; do isa $f; done
 for f in bbox; do isa $f; done
 # the data-preparation unit (csrc/vnet_tools.h): read for spills and scratch only
 for f in morph; do isa $f; done
+# the surface-distance unit (csrc/vnet_surface.h): read for spills and scratch only
+for f in surface; do isa $f; done
 wait
 python3 - "$TMP" > "$OUT" <<'PY'
 import glob, os, re, subprocess, sys

@@ -219,9 +219,9 @@ def abi_pointer_table():
 
 
 # HOST pointers of the ABI (not device buffers): the job array of the grouped filter gradient, the two result ints of vnet_packed_dims,
-# the values of vnet_select_bits (copied into the kernel's arguments)
+# the values of vnet_select_bits and the ranks of vnet_list_select (both copied into the kernel's arguments)
 HOST_POINTERS = {("vnet_conv_wgrad_b16_group", "jobs"), ("vnet_packed_dims", "CQ"), ("vnet_packed_dims", "NP"),
-                 ("vnet_select_bits", "values")}
+                 ("vnet_select_bits", "values"), ("vnet_list_select", "ranks")}
 
 
 class RecordingLib(object):

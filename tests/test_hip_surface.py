@@ -1,4 +1,4 @@
-"""-m gpu: the kernels of csrc/vnet_surface.h (libvnet_surface.so) through the ops of vnet_tensorflow_amd/surface.py against the NumPy
+"""-m gpu: the kernels of csrc/vnet_surface.h through the ops of vnet_tensorflow_amd/surface.py against the NumPy
 rules of vnet_tensorflow_amd/score.py.  Every comparison is `==` (np.array_equal, +inf included) but the sums of roots, which are held
 to the derived bound (n + 2) 2^-52 relative: at most 1 ulp (2^-52) per root on either side, (n - 1) 2^-53 per summation order."""
 import csv

@@ -1,14 +1,12 @@
-"""-m gpu: guard bands (tests/guard.py) around the five pointer-taking entry points of csrc/vnet_surface.h (libvnet_surface.so), called
-the way the product calls them (the ops of vnet_tensorflow_amd/surface.py inside guarded(arena, modules=(surface,)): inputs, outputs
-and scratch of EXACTLY the queried size are carved from the arena).  guard.guarded records libvnet_hip.so only, so every case wraps
-surface.lib in a recorder of its own: the entry points called go to the same list, and every device pointer must lie inside the arena.
-Checked by guard.check_case: (a) every guard byte intact and no input modified, (b) every output byte written, (c) results against
-the NumPy rules (vnet_tensorflow_amd/score.py), (d) bit-identical results on a 0xFF and a 0x00 pre-fill of outputs and scratch.
+"""-m gpu: guard bands (tests/guard.py) around the five pointer-taking entry points of csrc/vnet_surface.h, called the way the product
+calls them (the ops of vnet_tensorflow_amd/surface.py inside guarded(arena, modules=(surface,)): inputs, outputs and scratch of
+EXACTLY the queried size are carved from the arena).  Checked: (a) every guard byte intact and no input modified, (b) every output
+byte written, (c) results against the NumPy rules (vnet_tensorflow_amd/score.py), (d) bit-identical results on a 0xFF and a 0x00
+pre-fill of outputs and scratch, (e) a case calls its own entry point and no other.
 On (b): an output element that is legitimately all 0xFF reads as "never written" (tests/test_hip_bbox_guard.py explains).  None occurs
 here: no mask word has all 64 bits set (rows of 65 voxels or of one: the high bits are 0; the surfaces are sparse), a squared distance is
-never a NaN pattern (+inf is 0x7FF0...), counts are >= 0, the selected elements and the sums are finite or +inf."""
-import os
-
+never a NaN pattern (+inf is 0x7FF0...), counts are >= 0, the selected elements and the sums are finite or +inf.
+CASES (entry points a case must reach, function) is what the ledger test in tests/test_abi_ledger.py reads."""
 import numpy as np
 import pytest
 import torch
@@ -18,43 +16,7 @@ from vnet_tensorflow_amd import score as SC, surface
 
 pytestmark = pytest.mark.gpu
 SHAPES = {"5x7x65": (5, 7, 65), "1x1x1": (1, 1, 1)}
-HOST_POINTERS = {("vnet_list_select", "ranks")}
 SP = (0.7, 0.7, 2.5)
-
-
-class _Recording(object):
-    """Stands in for surface.lib(): records the entry points called; a device pointer outside the arena is an error."""
-
-    def __init__(self, real, arena, calls):
-        table = guard.pointer_entry_points(os.path.join(guard.ROOT, surface.HEADER))
-        self.__dict__.update(_real=real, _arena=arena, _calls=calls, _table=table)
-
-    def __getattr__(self, name):
-        fn, params = getattr(self._real, name), self._table.get(name)
-        if params is None:                     # (a size query)
-            return fn
-
-        def call(*args):
-            self._calls.append(name)
-            for (pname, ptr, _const, _typ), a in zip(params, args):
-                if not ptr or pname == "stream" or (name, pname) in HOST_POINTERS or a is None:
-                    continue
-                if self._arena.find(a) is None:
-                    raise guard.GuardError("%s: argument `%s` (0x%x) is not a tensor of the arena" % (name, pname, a))
-            return fn(*args)
-        return call
-
-
-def _recorded(fn):
-    def run(h):
-        real = surface.lib
-        rec = _Recording(real(), h.arena, h.calls)
-        surface.lib = lambda: rec
-        try:
-            return fn(h)
-        finally:
-            surface.lib = real
-    return run
 
 
 def _mask(shape):
@@ -70,6 +32,7 @@ def _bits(shape):
         t = h.g(label, dtype=torch.int32)
         for klass in (0, 2):
             assert np.array_equal(surface.surface_bits(t, klass).cpu().numpy(), SC.pack(SC.surface_mask(label, klass)))
+        assert set(h.calls) == {"vnet_surface_bits"}
     return run
 
 
@@ -79,6 +42,7 @@ def _edt2(shape):
         got = surface.edt2(h.g(SC.pack(m), dtype=torch.int64), shape[2], SP)
         assert h.ws_requests == [12 * m.size + (4 * m.size) % 8]
         assert np.array_equal(got.cpu().numpy(), SC.edt2(m, SP))
+        assert set(h.calls) == {"vnet_edt2"}
     return run
 
 
@@ -94,6 +58,7 @@ def _gather(shape):
             out = surface.empty_list(cap, t.device)
             _, n = surface.gather(t, bits, shape[2], out=out)
             assert int(n) == len(want) and np.array_equal(out.cpu().numpy(), np.concatenate([want[:cap], np.zeros(max(0, cap - len(want)))]))
+        assert set(h.calls) == {"vnet_surface_gather"}                     # (popcounts sizes the first list through it as well)
     return run
 
 
@@ -108,6 +73,7 @@ def _select(shape):
         v = _list(shape)
         ranks = [0, len(v) - 1, SC.hd95_rank(len(v))]
         assert np.array_equal(surface.kth(h.g(v, dtype=torch.float64), ranks).cpu().numpy(), SC.kth(v, ranks))
+        assert set(h.calls) == {"vnet_list_select"}
     return run
 
 
@@ -116,22 +82,17 @@ def _root_sum(shape):
         v = _list(shape)[1:]
         got, want = surface.root_sum(h.g(v, dtype=torch.float64)).item(), np.sqrt(v).sum()
         assert abs(got - want) <= (len(v) + 2) * 2.0 ** -52 * want
+        assert set(h.calls) == {"vnet_list_root_sum"}
     return run
 
 
 CASES = {}
 for _name, _shape in SHAPES.items():
-    CASES["bits " + _name] = (("vnet_surface_bits",), _recorded(_bits(_shape)))
-    CASES["edt2 " + _name] = (("vnet_edt2",), _recorded(_edt2(_shape)))
-    CASES["gather " + _name] = (("vnet_surface_gather",), _recorded(_gather(_shape)))
-    CASES["select " + _name] = (("vnet_list_select",), _recorded(_select(_shape)))
-    CASES["root sum " + _name] = (("vnet_list_root_sum",), _recorded(_root_sum(_shape)))
-
-
-def test_every_entry_point_of_the_header_has_a_case():
-    declared = set(guard.pointer_entry_points(os.path.join(guard.ROOT, surface.HEADER)))
-    assert declared == {e for entries, _ in CASES.values() for e in entries} and len(declared) == 5
-    assert declared == {n for n in surface.SIGNATURES_SURFACE if not n.endswith("_ws_bytes")}
+    CASES["bits " + _name] = (("vnet_surface_bits",), _bits(_shape))
+    CASES["edt2 " + _name] = (("vnet_edt2",), _edt2(_shape))
+    CASES["gather " + _name] = (("vnet_surface_gather",), _gather(_shape))
+    CASES["select " + _name] = (("vnet_list_select",), _select(_shape))
+    CASES["root sum " + _name] = (("vnet_list_root_sum",), _root_sum(_shape))
 
 
 @pytest.mark.parametrize("cid", sorted(CASES))

@@ -1,6 +1,6 @@
 """CPU tests of the surface-distance scores (vnet_tensorflow_amd/score.py: surface_mask, edt2, surface_distances, Accuracy's SURFACE mode;
-batch_evaluate.py's --mode SURFACE) and the ledger of csrc/vnet_surface.h, the header of libvnet_surface.so (the library is not in
-_lib.HEADERS, so tests/test_abi_ledger.py does not see it; its RULE table is applied here)."""
+batch_evaluate.py's --mode SURFACE) and what csrc/vnet_surface.h alone has to say beside its row of tests/test_abi_ledger.py (needs
+the built library)."""
 import csv
 import ctypes
 import os
@@ -11,7 +11,6 @@ import torch
 from scipy import ndimage
 
 from tests import guard
-from tests.test_abi_ledger import RULE, _result_types
 from tests.test_score_host import CFG, StandIn, _sweep_folders
 from vnet_tensorflow_amd import _lib, batch_evaluate as BE, data, score as SC, surface
 
@@ -185,31 +184,17 @@ def test_get_args_and_the_constructor_take_surface(tmp_path):
     assert BE.columns(["DICE"]) == ["Case", "DICE", "Jaccard"] and BE.columns(["ITEM"]) == ["Case"] + BE.ITEM_COLUMNS
 
 
-# ---- csrc/vnet_surface.h: declared == bound == exported ---------------------------------------------------------------------------------
-def test_surface_header_ledger():
-    path = os.path.join(ROOT, surface.HEADER)
-    fns = guard.header_functions(path)
-    assert set(fns) == set(surface.SIGNATURES_SURFACE) and len(fns) == 9
-    exported = ctypes.CDLL(surface.LIB_PATH)
-    assert not [n for n in fns if not hasattr(exported, n)]
-    results = _result_types(path)
-    for name, params in fns.items():
-        res, args = surface.SIGNATURES_SURFACE[name]
-        want = [ctypes.c_void_p if (p[1] and p[3].replace(" ", "") != "constchar*") else RULE[p[3]] for p in params]
-        assert args == want, (name, args, want)
-        assert res is RULE[results[name]] and (res is ctypes.c_size_t) == name.endswith("_ws_bytes"), name
-    pointer = guard.pointer_entry_points(path)
-    assert set(pointer) == {n for n in fns if not n.endswith("_ws_bytes")}
-    assert all(ps[-1][0] == "stream" for ps in pointer.values())
-    # a library of its own: none of these names is in the training library's registry, the header is not published
-    assert not set(fns) & set(_lib.all_signatures()) and surface.HEADER not in [h for h, _ in _lib.HEADERS]
-    assert not os.path.exists(os.path.join(ROOT, "include", "vnet_surface.h")) and os.path.basename(surface.LIB_PATH) == "libvnet_surface.so"
+# ---- csrc/vnet_surface.h: what its row of tests/test_abi_ledger.py does not say --------------------------------------------------------
+def test_surface_lives_in_the_one_library():
+    assert surface.HEADER in [h for h, _ in _lib.HEADERS] and surface.lib is _lib.lib and not hasattr(surface, "LIB_PATH")
+    names = set(guard.header_functions(os.path.join(ROOT, surface.HEADER)))
+    assert len(names) == 9 and names <= set(_lib.all_signatures())
     main = ctypes.CDLL(_lib.LIB_PATH)
-    assert not [n for n in fns if hasattr(main, n)]
+    assert not [n for n in names if not hasattr(main, n)]
+    assert not surface.HEADER.startswith("include/") and not os.path.exists(os.path.join(ROOT, "include", "vnet_surface.h"))
     mk = open(os.path.join(ROOT, "vnet_tensorflow_amd", "csrc", "Makefile")).read()
-    for word in ("SURF_SRCS = surface.hip", "SURF_OBJS", "SURF_LIB  = ../libvnet_surface.so", "$(SURF_OBJS): vnet_surface.h"):
-        assert word in mk, word
-    head = open(path).read()
+    assert "libvnet_surface" not in mk and "SURF_" not in mk
+    head = open(os.path.join(ROOT, surface.HEADER)).read()
     assert "#define VNET_SURFACE_MAX_AXIS %d" % surface.MAX_AXIS in head and "#define VNET_SURFACE_MAX_RANKS %d" % surface.MAX_RANKS in head
     assert surface.MAX_AXIS >= 2048
     src = open(os.path.join(ROOT, "vnet_tensorflow_amd", "csrc", "surface.hip")).read()
@@ -218,7 +203,7 @@ def test_surface_header_ledger():
 
 def test_error_codes_need_no_device():
     """VNET_E_BADARG (-1), VNET_E_UNSUPPORTED (-2), VNET_E_WORKSPACE (-3) before any launch, in that order."""
-    L = surface.lib()
+    L = _lib.lib()
     one, odd, big = ctypes.c_void_p(16), ctypes.c_void_p(20), 1 << 40
     assert L.vnet_surface_bits(None, 0, one, 5, 4, 3, None) == -1 and L.vnet_surface_bits(one, -1, one, 5, 4, 3, None) == -1
     assert L.vnet_surface_bits(one, 0, odd, 5, 4, 3, None) == -1 and L.vnet_surface_bits(one, 0, one, 0, 4, 3, None) == -1

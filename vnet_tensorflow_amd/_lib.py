@@ -218,6 +218,20 @@ SIGNATURES_TOOLS = {
     "vnet_unpack_bits": (_i, [_vp, _vp, _i, _i, _i, _vp]),
 }
 
+# csrc/vnet_surface.h: the package's own entry points too, not published under include/ (the SURFACE scores of Batch_Evaluate,
+# surface.py), same library
+SIGNATURES_SURFACE = {
+    "vnet_surface_bits": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
+    "vnet_edt2_ws_bytes": (_sz, [_i, _i, _i]),
+    "vnet_edt2": (_i, [_vp, _vp, _d, _d, _d, _i, _i, _i, _vp, _sz, _vp]),
+    "vnet_surface_gather_ws_bytes": (_sz, [_i, _i, _i]),
+    "vnet_surface_gather": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _sz, _vp]),
+    "vnet_list_select_ws_bytes": (_sz, [_i64, _i]),
+    "vnet_list_select": (_i, [_vp, _i64, _vp, _i, _vp, _vp, _sz, _vp]),
+    "vnet_list_root_sum_ws_bytes": (_sz, [_i64]),
+    "vnet_list_root_sum": (_i, [_vp, _i64, _vp, _vp, _sz, _vp]),
+}
+
 
 # Every header of the library's C ABI, in the order they were published, with the table that binds it (path relative to the repository
 # root).  lib() binds them all, tests/guard.py reads the pointer parameters of all, tests/test_abi_ledger.py holds each row to its header.
@@ -235,6 +249,7 @@ HEADERS = (
     ("include/vnet_hip_deform_sample.h", SIGNATURES_DEFORM_SAMPLE),
     ("vnet_tensorflow_amd/csrc/vnet_bbox.h", SIGNATURES_BBOX),
     ("vnet_tensorflow_amd/csrc/vnet_tools.h", SIGNATURES_TOOLS),
+    ("vnet_tensorflow_amd/csrc/vnet_surface.h", SIGNATURES_SURFACE),
 )
 
 

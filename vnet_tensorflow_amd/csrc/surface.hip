@@ -1,4 +1,4 @@
-// surface.hip -- the surface-distance scores of Batch_Evaluate on the device (csrc/vnet_surface.h, libvnet_surface.so), gfx950.
+// surface.hip -- the surface-distance scores of Batch_Evaluate on the device (csrc/vnet_surface.h, part of libvnet_hip.so), gfx950.
 //   vnet_surface_bits   : one wave per word: lane k reads voxel z = 64 w + k of row (x, y) and its four in-plane neighbours, five ballots
 //                         are the class mask's word and its neighbour rows' words; the two z neighbours come from the word itself
 //                         shifted by one bit, the bits carried in from words w - 1 and w + 1 read by lanes 0 and 1 (a sixth ballot).

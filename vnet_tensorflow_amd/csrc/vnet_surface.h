@@ -1,5 +1,5 @@
-/* vnet_surface.h -- the package's OWN entry points of libvnet_surface.so, a library beside libvnet_hip.so and not part of the
- * published C ABI under include/: what the SURFACE scores of Batch_Evaluate (Hausdorff distance, its 95th percentile, average symmetric
+/* vnet_surface.h -- the package's OWN entry points for the surface-distance scores: part of libvnet_hip.so, not part of the
+ * published C ABI under include/.  What the SURFACE scores of Batch_Evaluate (Hausdorff distance, its 95th percentile, average symmetric
  * surface distance) run on the device.  A label map becomes the packed surface of a class mask, the surface becomes an exact squared
  * Euclidean distance field in fp64, the field is read at the voxels of the other map's surface into a list, and the list gives up an
  * order statistic and the sum of its roots.  The rules: vnet_tensorflow_amd/score.py and DESIGN.md section 6j.

@@ -1,6 +1,6 @@
-"""ctypes binding of libvnet_surface.so (csrc/vnet_surface.h, csrc/surface.hip) and its device ops: what the SURFACE scores of
-Batch_Evaluate run on the device (vnet_tensorflow_amd/score.py states the rules).  A library of its own beside
-libvnet_hip.so: the header is the package's own, not part of the published C ABI, and none of this is in _lib.HEADERS.
+"""The device ops over csrc/vnet_surface.h (csrc/surface.hip): what the SURFACE scores of Batch_Evaluate run on the device
+(vnet_tensorflow_amd/score.py states the rules).  The header is the package's own, not part of the published C
+ABI; its entry points live in libvnet_hip.so and are bound by _lib.lib() like every other row of _lib.HEADERS.
 
 Same conventions as _lib / ops: there is NO fallback -- a missing library or a kernel that reports an error raises VnetHipError,
 nothing routes to PyTorch or the CPU; ops launch on torch's current stream of the calling thread; outputs are allocated through this
@@ -10,56 +10,17 @@ A label map is an int32 device tensor [X,Y,Z].  A PACKED MASK is an int64 tensor
 word w is voxel z = 64 w + k, the unused high bits of a row's last word are zero.  The word count loses Z, so the ops that take a mask
 take Z beside it.  A list is a 1-D float64 device tensor of non-negative numbers."""
 import ctypes
-import os
 
 import torch
 
 from . import ops
-from ._lib import VnetHipError, check
+from ._lib import VnetHipError, check, lib
+from .morph import words
 from .ops import _thread_stream as _stream
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("VNET_SURFACE_LIB") or os.path.join(_HERE, "libvnet_surface.so")
-HEADER = "vnet_tensorflow_amd/csrc/vnet_surface.h"
-
-_vp, _i, _i64, _sz, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_double
-
-# name -> (restype, argtypes) : every symbol csrc/vnet_surface.h declares (tests/test_surface_host.py holds the table to the header)
-SIGNATURES_SURFACE = {
-    "vnet_surface_bits": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
-    "vnet_edt2_ws_bytes": (_sz, [_i, _i, _i]),
-    "vnet_edt2": (_i, [_vp, _vp, _d, _d, _d, _i, _i, _i, _vp, _sz, _vp]),
-    "vnet_surface_gather_ws_bytes": (_sz, [_i, _i, _i]),
-    "vnet_surface_gather": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _sz, _vp]),
-    "vnet_list_select_ws_bytes": (_sz, [_i64, _i]),
-    "vnet_list_select": (_i, [_vp, _i64, _vp, _i, _vp, _vp, _sz, _vp]),
-    "vnet_list_root_sum_ws_bytes": (_sz, [_i64]),
-    "vnet_list_root_sum": (_i, [_vp, _i64, _vp, _vp, _sz, _vp]),
-}
+HEADER = "vnet_tensorflow_amd/csrc/vnet_surface.h"        # its row of _lib.HEADERS
 
 MAX_AXIS, MAX_RANKS, MAX_VOXELS = 2048, 4, 2 ** 31 - 1        # VNET_SURFACE_MAX_AXIS, VNET_SURFACE_MAX_RANKS
-
-_surface = None
-
-
-def lib():
-    """The loaded libvnet_surface.so (raises if it has not been built: there is no fallback path)."""
-    global _surface
-    if _surface is None:
-        if not os.path.exists(LIB_PATH):
-            raise VnetHipError("libvnet_surface.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(hipcc, gfx950).  The HIP library is the only compute path." % LIB_PATH)
-        # torch (imported above) has loaded its own libamdhip64 by now: both libraries and torch's streams live in ONE HIP runtime
-        L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES_SURFACE.items():
-            fn = getattr(L, name)              # AttributeError if a declared symbol is not exported
-            fn.restype, fn.argtypes = res, args
-        _surface = L
-    return _surface
-
-
-def words(Z):
-    return (int(Z) + 63) // 64
 
 
 def _device(x, what):
