@@ -19,7 +19,10 @@ What differs from the reference, on purpose:
     added.
   * --mode SURFACE (not in the reference) adds HD, HD95 and ASSD of the foreground surface in physical units, by the rules of score.py;
     on a device model an exact Euclidean distance transform runs there (vnet_tensorflow_amd/surface.py).  A case in which exactly one
-    of the two maps has no foreground scores inf, and so does the `average` row."""
+    of the two maps has no foreground scores inf, and so does the `average` row.
+  * --postprocess PATH (not in the reference) names the YAML of a post-processing pipeline (vnet_tensorflow_amd/postprocess.py) and
+    overrides EvaluationSetting.Postprocess: the label is cleaned class by class on the device before on_label hands it over, so the
+    scores and the files of write_labels=True are those of the post-processed label."""
 import argparse
 import copy
 import csv
@@ -100,7 +103,8 @@ class Batch_Evaluate:
                  device=None,
                  write_labels=False,
                  verbose=False,
-                 cache_fields=True):
+                 cache_fields=True,
+                 postprocess=None):
         self.config_json = config_json               # a path, or the parsed dict
         self.model_folder = model_folder
         self.output_folder = output_folder
@@ -130,6 +134,9 @@ class Batch_Evaluate:
         self.verbose = bool(verbose)
         # SURFACE: keep every case's ground-truth surface and its squared distance field (8 bytes per voxel) over the sweep
         self.cache_fields = bool(cache_fields)
+        # the YAML of a post-processing pipeline (postprocess.py): overrides EvaluationSetting.Postprocess; None keeps the config's
+        assert postprocess is None or isinstance(postprocess, str)
+        self.postprocess = postprocess
 
     @property
     def model_folder(self):
@@ -173,6 +180,8 @@ class Batch_Evaluate:
         if self.patch_layer is not None:
             shape[2] = int(self.patch_layer)
         T["PatchShape"] = shape
+        if self.postprocess is not None:
+            cfg.setdefault("EvaluationSetting", {})["Postprocess"] = self.postprocess
         return cfg
 
     def build_model(self, cfg):
@@ -323,6 +332,8 @@ def get_args(argv=None):
     parser.add_argument('--tolerance', dest='tolerance', help='Centroid distance below which an item is found (ITEM)', type=float,
                         metavar='FLOAT', default=3)
     parser.add_argument('--gpu', dest='gpu', help='Index of the HIP device', type=int, metavar='INT', default=0)
+    parser.add_argument('--postprocess', dest='postprocess', help='YAML of a post-processing pipeline (overrides '
+                        'EvaluationSetting.Postprocess)', type=str, metavar='PATH', default=None)
     args = parser.parse_args(argv)
     if args.verbose:
         args_dict = vars(args)
@@ -338,7 +349,8 @@ def main(args):
                         stride_layer_max=args.stride_layer_max, stride_inplane_min=args.stride_inplane_min,
                         stride_inplane_max=args.stride_inplane_max, patch_size=args.patch_size, patch_layer=args.patch_layer,
                         checkpoint_min=args.checkpoint_min, checkpoint_max=args.checkpoint_max, batch_size=args.batch,
-                        mode=args.mode, tolerance=args.tolerance, device="cuda:%d" % args.gpu, verbose=args.verbose)
+                        mode=args.mode, tolerance=args.tolerance, device="cuda:%d" % args.gpu, verbose=args.verbose,
+                        postprocess=args.postprocess)
     return be.Execute()
 
 

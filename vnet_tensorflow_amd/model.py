@@ -340,6 +340,9 @@ class image2label(object):
         self.evaluate_lcc = E.get('LargestConnectedComponent', False)
         self.evaluate_volume_threshold = E.get('VolumeThreshold', False)
         self.evaluate_pipeline = E.get('Pipeline')
+        # extension (opt-in): the YAML of a post-processing pipeline run on the label before it is copied out (postprocess.py, DESIGN
+        # section 6k); absent or empty: none
+        self.evaluate_postprocess = E.get('Postprocess') or None
         # extension (opt-in): the evaluate pipeline and the window crops on a case uploaded once (prepare.prepare_on_device, DESIGN
         # section 6e).  Off by default: the device sums a channel's statistics in another order than NumPy
         self.prepare_on_device = bool(E.get('PrepareOnDevice', False))
@@ -1090,7 +1093,7 @@ class image2label(object):
     # -- reference model.py:817-977 (array in / arrays out) ----------------------------------------------------------
     @in_context
     def evaluate_single_3D(self, images_np, back_size=None, back_ratio=None, largest_component=False, volume_threshold=None,
-                           spacing=None, extent=None, on_label=None):
+                           spacing=None, extent=None, postprocess=None, on_label=None):
         """images_np float32 [X,Y,Z,Cin] -> (label int64 [X,Y,Z], softmax float32 [K,X,Y,Z]).
         Patch enumeration, the duplicated last batch and argmax-of-summed-softmax follow
         model.py:866-937 exactly; accumulation runs on the GPU.
@@ -1102,6 +1105,8 @@ class image2label(object):
         of the grid the label is returned on.  They see the volume the caller gets: on the back_size branch the resampled label, else
         the label cropped to images_np's extent, and to `extent` where that is smaller (evaluate(): the input file's size, which a
         Padding transform may have grown).  The label is then the 0/1 map.  With neither filter nothing changes.
+        postprocess: a step list of postprocess.py (postprocess.build), run where the label filters run and after them -- on the
+        kernels for a device model, on the module's restatements for a CPU model; class values are kept.  None or empty: nothing changes.
         images_np may also be a float32 tensor [X,Y,Z,Cin] on the model's device (a case prepared there, prepare.prepare_on_device):
         the same windows in the same batches, each cut on the device by ops.crop_window into its slot of the batch -- no worker
         threads, no pinned staging, no prepare_batch -- and the label formed by ops.argmax_label.  The results are NumPy arrays with
@@ -1110,13 +1115,20 @@ class image2label(object):
         with -- after the way back and the label filters, before the copy to the host (batch_evaluate scores it there).  What the
         function returns does not depend on it; None: nothing is formed for it."""
         vt = volume_threshold if volume_threshold is not None and volume_threshold > 0 else None
-        filtered = bool(largest_component) or vt is not None
+        legacy = bool(largest_component) or vt is not None
+        filtered = legacy or bool(postprocess)
         sp = tuple(float(v) for v in spacing) if spacing is not None else (1.0, 1.0, 1.0)
 
         def filters(label):
             if largest_component:
-                return ops.largest_component(label, classes=self.output_channel_num, min_volume=vt, spacing=sp)
-            return ops.volume_threshold(label, vt, sp)
+                label = ops.largest_component(label, classes=self.output_channel_num, min_volume=vt, spacing=sp)
+            elif legacy:
+                label = ops.volume_threshold(label, vt, sp)
+            if postprocess:
+                from . import postprocess as vpost
+                label = vpost.run(postprocess, label if label.dtype == torch.int32 else label.to(torch.int32), sp,
+                                  classes=self.output_channel_num)
+            return label
         def seen(label):
             if on_label is not None:
                 on_label(label if label.dtype == torch.int32 else label.to(torch.int32))
@@ -1250,6 +1262,17 @@ class image2label(object):
         vol_np, cnt_np = vol.cpu().numpy(), cnt.cpu().numpy()
         return label_np, (np.moveaxis(vol_np, -1, 0) / np.float32(cnt_np))[(slice(None),) + sl]
 
+    def evaluate_postprocess_steps(self):
+        """The step list of EvaluationSetting.Postprocess (postprocess.build), or None."""
+        path = getattr(self, "evaluate_postprocess", None)
+        if not path:
+            return None
+        cached = getattr(self, "_postprocess_steps", None)
+        if cached is None or cached[0] != path:                # (read once per file, not once per case)
+            from . import postprocess as vpost
+            cached = self._postprocess_steps = (path, vpost.build(path) or None)
+        return cached[1]
+
     def evaluate_pipeline_transforms(self):
         """(transform list | None, whether it changes the grid) of EvaluationSetting.Pipeline: the 'evaluate' transform list of the
         reference's YAML (model.py:1142-1167).  Resample runs on the device here (this is the main thread and no stream capture is
@@ -1275,6 +1298,9 @@ class image2label(object):
         on_device = {}
         if self.evaluate_lcc or vt is not None:
             on_device = dict(largest_component=bool(self.evaluate_lcc), volume_threshold=vt, spacing=spacing, extent=size)
+        steps = self.evaluate_postprocess_steps()
+        if steps:
+            on_device.update(postprocess=steps, spacing=spacing, extent=size)
         if on_label is not None:
             on_device["on_label"] = on_label
         prepared = None
