@@ -22,7 +22,11 @@ What differs from the reference, on purpose:
     of the two maps has no foreground scores inf, and so does the `average` row.
   * --postprocess PATH (not in the reference) names the YAML of a post-processing pipeline (vnet_tensorflow_amd/postprocess.py) and
     overrides EvaluationSetting.Postprocess: the label is cleaned class by class on the device before on_label hands it over, so the
-    scores and the files of write_labels=True are those of the post-processed label."""
+    scores and the files of write_labels=True are those of the post-processed label.
+  * --mirror AXES, --window_weights KIND [KIND ...], --window_sigma S (not in the reference; vnet_tensorflow_amd/window.py): mirrored
+    passes and Gaussian window weights of the sliding window.  They override EvaluationSetting.Mirror / WindowWeights / WindowSigma;
+    several window weights are a further dimension of the sweep, inside the stride loop.  A CSV keeps the reference's name while the
+    weights are uniform and no mirror is set; otherwise the name says so, e.g. `..._window-gaussian_mirror-012.csv`."""
 import argparse
 import copy
 import csv
@@ -104,7 +108,10 @@ class Batch_Evaluate:
                  write_labels=False,
                  verbose=False,
                  cache_fields=True,
-                 postprocess=None):
+                 postprocess=None,
+                 mirror=None,
+                 window_weights=None,
+                 window_sigma=None):
         self.config_json = config_json               # a path, or the parsed dict
         self.model_folder = model_folder
         self.output_folder = output_folder
@@ -137,6 +144,17 @@ class Batch_Evaluate:
         # the YAML of a post-processing pipeline (postprocess.py): overrides EvaluationSetting.Postprocess; None keeps the config's
         assert postprocess is None or isinstance(postprocess, str)
         self.postprocess = postprocess
+        # window.py: a flat axis list, the window weights to sweep (one name or several), the Gaussian's sigma; None keeps the config's
+        from . import window as vwin
+        self.mirror = None if mirror is None else [int(a) for a in mirror]
+        if self.mirror is not None:
+            vwin.flip_sets(self.mirror)                  # (refuses an axis outside 0 .. 2 and a repeated one, by name)
+        if isinstance(window_weights, str):
+            window_weights = [window_weights]
+        self.window_weights = None if window_weights is None else list(window_weights)
+        assert self.window_weights is None or (self.window_weights and len(set(self.window_weights)) == len(self.window_weights) and
+                                               all(k in vwin.KINDS for k in self.window_weights)), window_weights
+        self.window_sigma = window_sigma
 
     @property
     def model_folder(self):
@@ -182,7 +200,27 @@ class Batch_Evaluate:
         T["PatchShape"] = shape
         if self.postprocess is not None:
             cfg.setdefault("EvaluationSetting", {})["Postprocess"] = self.postprocess
+        if self.mirror is not None:
+            cfg.setdefault("EvaluationSetting", {})["Mirror"] = list(self.mirror)
+        if self.window_sigma is not None:
+            cfg.setdefault("EvaluationSetting", {})["WindowSigma"] = self.window_sigma
         return cfg
+
+    def weights(self, model):
+        """The window weights of the sweep: the argument's, else the one the config sets on the model."""
+        return list(self.window_weights) if self.window_weights is not None else [getattr(model, "evaluate_window_weights", "uniform")]
+
+    @staticmethod
+    def csv_name(step, stride_inplane, stride_layer, window_weights="uniform", masks=(0,)):
+        """The reference's file name; with other than uniform weights or with mirrored passes, a suffix that says so (the mirror as the
+        axes of its masks: `mirror-012` every subset of three axes, `mirror-01` the one joint flip [[0, 1]] or both axes' subsets)."""
+        name = "result_checkpoint-%d_stride_inplane-%d_stride_layer-%d" % (step, stride_inplane, stride_layer)
+        axes = "".join(str(a) for a in range(3) if any(m >> a & 1 for m in masks))
+        if window_weights != "uniform" or axes:
+            name += "_window-%s" % window_weights
+        if axes:
+            name += "_mirror-%s" % axes
+        return name + ".csv"
 
     def build_model(self, cfg):
         """The ONE model of the sweep."""
@@ -256,11 +294,23 @@ class Batch_Evaluate:
         cases, cache = self.cases(), {}
         max_dice = max_jaccard = 0
         first = {"ckpt": os.path.basename(ckpts[0][1]), "stride_inplane": self.stride_inplane_min, "stride_layer": self.stride_layer_min}
+        from . import window as vwin
+        # (set on the model like the stride: a model that read the config holds the same values already)
+        if self.mirror is not None:
+            model.evaluate_mirror = list(self.mirror)
+        if self.window_sigma is not None:
+            model.evaluate_window_sigma = self.window_sigma
+        mirror = getattr(model, "evaluate_mirror", None) or []
+        kinds, masks = self.weights(model), vwin.flip_sets(mirror)
+        swept = len(kinds) > 1            # the best-result dictionaries name the window weights and the mirror only when they are swept
+        if swept:
+            first.update(window_weights=kinds[0], mirror=list(mirror))
         best_dice_result, best_jaccard_result = dict(first), dict(first)
         for step, prefix in ckpts:
             model.load_checkpoint(prefix, with_optimizer=False)
-            for stride_inplane, stride_layer in self.strides():
+            for (stride_inplane, stride_layer), kind in ((s, k) for s in self.strides() for k in kinds):
                 model.evaluate_stride = [stride_inplane, stride_inplane, stride_layer]
+                model.evaluate_window_weights = kind
                 rows = []
                 for name in cases:
                     entry = self._case(model, name, cache)
@@ -275,9 +325,11 @@ class Batch_Evaluate:
                     rows.append(result)
                     if self.write_labels:
                         model.write_label(os.path.join(entry["dir"], self.evaluated_filename), label, entry["spacing"])
-                avg = write_csv(os.path.join(self._output_folder, "result_checkpoint-%d_stride_inplane-%d_stride_layer-%d.csv" % (
-                    step, stride_inplane, stride_layer)), self.mode, rows)
+                avg = write_csv(os.path.join(self._output_folder, self.csv_name(step, stride_inplane, stride_layer, kind, masks)),
+                                self.mode, rows)
                 here = {"ckpt": os.path.basename(prefix), "stride_inplane": stride_inplane, "stride_layer": stride_layer}
+                if swept:
+                    here.update(window_weights=kind, mirror=list(mirror))
                 if "DICE" in self.mode:
                     if avg["DICE"] > max_dice:
                         max_dice, best_dice_result = avg["DICE"], here
@@ -334,6 +386,12 @@ def get_args(argv=None):
     parser.add_argument('--gpu', dest='gpu', help='Index of the HIP device', type=int, metavar='INT', default=0)
     parser.add_argument('--postprocess', dest='postprocess', help='YAML of a post-processing pipeline (overrides '
                         'EvaluationSetting.Postprocess)', type=str, metavar='PATH', default=None)
+    parser.add_argument('--mirror', dest='mirror', help='Axes to mirror: every subset of them is a pass of every batch (overrides '
+                        'EvaluationSetting.Mirror)', type=int, nargs='*', choices=[0, 1, 2], metavar='AXIS', default=None)
+    parser.add_argument('--window_weights', dest='window_weights', help='Window weights to sweep (overrides '
+                        'EvaluationSetting.WindowWeights)', nargs='+', choices=["uniform", "gaussian"], default=None)
+    parser.add_argument('--window_sigma', dest='window_sigma', help='Sigma of the gaussian window weights in units of the window size '
+                        '(overrides EvaluationSetting.WindowSigma)', type=float, metavar='FLOAT', default=None)
     args = parser.parse_args(argv)
     if args.verbose:
         args_dict = vars(args)
@@ -350,7 +408,8 @@ def main(args):
                         stride_inplane_max=args.stride_inplane_max, patch_size=args.patch_size, patch_layer=args.patch_layer,
                         checkpoint_min=args.checkpoint_min, checkpoint_max=args.checkpoint_max, batch_size=args.batch,
                         mode=args.mode, tolerance=args.tolerance, device="cuda:%d" % args.gpu, verbose=args.verbose,
-                        postprocess=args.postprocess)
+                        postprocess=args.postprocess, mirror=args.mirror, window_weights=args.window_weights,
+                        window_sigma=args.window_sigma)
     return be.Execute()
 
 

@@ -346,6 +346,12 @@ class image2label(object):
         # extension (opt-in): the evaluate pipeline and the window crops on a case uploaded once (prepare.prepare_on_device, DESIGN
         # section 6e).  Off by default: the device sums a channel's statistics in another order than NumPy
         self.prepare_on_device = bool(E.get('PrepareOnDevice', False))
+        # extension (opt-in): mirrored passes and window weights of the sliding window (window.py).  Mirror: a list
+        # of axes (every subset is a pass) or a list of axis sets; WindowWeights: "uniform" or "gaussian"; WindowSigma: the Gaussian's
+        # sigma in units of the window's size, a number or three.  Absent, [] and "uniform": the reference's plain windows
+        self.evaluate_mirror = E.get('Mirror') or []
+        self.evaluate_window_weights = E.get('WindowWeights') or "uniform"
+        self.evaluate_window_sigma = E.get('WindowSigma', 0.125)
         self._print("{}: Reading configuration file complete".format(_now()))
 
     # -- reference model.py:297-630 (network + loss head; its summaries and metrics: _log_step) ---------------
@@ -1113,7 +1119,12 @@ class image2label(object):
         the values of the array path.
         on_label: a callable that receives the label as an int32 tensor on the device, on the grid and with the values it is returned
         with -- after the way back and the label filters, before the copy to the host (batch_evaluate scores it there).  What the
-        function returns does not depend on it; None: nothing is formed for it."""
+        function returns does not depend on it; None: nothing is formed for it.
+        self.evaluate_mirror / evaluate_window_weights / evaluate_window_sigma (EvaluationSetting.Mirror / WindowWeights /
+        WindowSigma; window.py): with a mirror or "gaussian" weights every batch runs once per mask of window.flip_sets, identity
+        first -- the mirrored batch is cut by window.crop_flip, goes through _infer as a batch of its own, and window.accumulate adds
+        each window's softmax, mirrored back and weighted, to the same sums.  Everything behind the sums is untouched.  With neither,
+        the loops below are the reference's, bit for bit, and libvnet_window.so is not loaded."""
         vt = volume_threshold if volume_threshold is not None and volume_threshold > 0 else None
         legacy = bool(largest_component) or vt is not None
         filtered = legacy or bool(postprocess)
@@ -1134,6 +1145,11 @@ class image2label(object):
                 on_label(label if label.dtype == torch.int32 else label.to(torch.int32))
             return label
         ps, st = list(self.patch_shape), list(self.evaluate_stride)
+        from . import window as vwin
+        masks = vwin.flip_sets(getattr(self, "evaluate_mirror", None))
+        wvec = vwin.weight_vectors(getattr(self, "evaluate_window_weights", None) or "uniform", ps,
+                                   getattr(self, "evaluate_window_sigma", 0.125))
+        windowed_passes = masks != [0] or wvec is not None
         pads = [(0, max(p - s, 0)) for s, p in zip(images_np.shape[:3], ps)]
         orig = tuple(int(v) for v in images_np.shape[:3])
         resident = isinstance(images_np, torch.Tensor)
@@ -1180,8 +1196,18 @@ class image2label(object):
             # one stream, one slot: the crops of a batch are enqueued behind the network's reads of the batch before it
             slot = torch.empty((max(len(bd['indexes']) for bd in batches),) + tuple(ps) + (images_np.shape[3],),
                                dtype=torch.float32, device=self.device)
+            wdev = vwin.device_weights(wvec, self.device)
             for bd in batches:
                 batch = slot[:len(bd['indexes'])]
+                if windowed_passes:
+                    # one pass per mask, identity first: each mirrored batch is a batch of its own in the network
+                    for mask in masks:
+                        for j, idx in enumerate(bd['indexes']):
+                            vwin.crop_flip(images_np, (idx[0], idx[2], idx[4]), ps, mask, out=batch[j])
+                        sm = self._infer(batch)
+                        for j, idx in enumerate(bd['indexes']):
+                            vwin.accumulate(sm[j], vol, cnt, (idx[0], idx[2], idx[4]), mask, wdev)
+                    continue
                 for j, idx in enumerate(bd['indexes']):
                     ops.crop_window(images_np, (idx[0], idx[2], idx[4]), ps, out=batch[j])
                 sm = self._infer(batch)
@@ -1201,7 +1227,27 @@ class image2label(object):
                 while q:
                     yield q.popleft().result()
             feeder = _DeviceFeeder(self.device, windowed())
+            wdev = vwin.device_weights(wvec, self.device)
+            slot = None
             for bd, (batch, _) in zip(batches, feeder):
+                if windowed_passes:
+                    # one pass per mask, identity first; a mirrored batch is cut from the uploaded batch's windows (each taken as
+                    # a volume at start 0) into a second slot, and is a batch of its own in the network
+                    for mask in masks:
+                        if mask == 0:
+                            flipped = batch
+                        else:
+                            if slot is None:
+                                slot = torch.empty((max(len(b['indexes']) for b in batches),) + tuple(batch.shape[1:]),
+                                                   dtype=torch.float32, device=batch.device)
+                            flipped = slot[:batch.shape[0]]
+                            for j in range(batch.shape[0]):
+                                vwin.crop_flip(batch[j], (0, 0, 0), ps, mask, out=flipped[j])
+                        sm = self._infer(flipped)
+                        for j, idx in enumerate(bd['indexes']):
+                            vwin.accumulate(sm[j], vol, cnt, (idx[0], idx[2], idx[4]), mask, wdev)
+                    feeder.step_done()
+                    continue
                 sm = self._infer(batch)
                 for j, idx in enumerate(bd['indexes']):
                     ops.accumulate_patch(sm[j], vol, cnt, (idx[0], idx[2], idx[4]))
